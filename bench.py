@@ -29,6 +29,17 @@ every rank's kernel times), `step_breakdown` (slowest rank's kernel vs the rest 
 Before the `--warmup` steps every rank spins `search_in` for >= 100 ms of wall time (untimed; `config.prewarm_ms`): at 8 GPUs
 a step is ~1.2 ms, so warm-up + timed region together are shorter than the clocks' ramp after an idle gap.
 
+A plain run measures the headline and nothing else.  `--full` adds every untimed extra, each in runs of its own: the plain-read
+ceiling (`roofline.read_ceiling_gbps`), the live `rocprofv3 --pmc FETCH_SIZE` pass (`roofline.traffic`; a plain run quotes the
+stored ratio), the other configs (`configs`, `configs_summary`; N = 1), the CPU baseline (`cpu_baseline`; N = 1) and the
+4 MiB-shard calls of `step_breakdown` (N > 1).  The `--no-*` options switch single extras of a `--full` run off.
+
+`--dump-outputs DIR` writes what the timed path returns - `search_in`'s bool, the one thing its caller receives - as float32
+arrays: DIR/found.npy, its answer in the last timed step (false: the needle is absent), and DIR/planted.npy, the answers of the
+same call on the same buffers to 16 fixed, seeded cases after everything the line reports (the needle planted whole or as a near
+miss at a seeded offset, the bytes restored after each case; `planted_cases`).  The inputs are seeded, so two builds can be
+compared output for output.
+
 stdout: ONE JSON line (rank 0).  Everything else goes to stderr.
 """
 import argparse
@@ -46,10 +57,33 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 SEED_HAY = 0x5EED0001
 SEED_NEEDLE = 0x5EED0002
+SEED_OUTPUTS = 0x5EED0003
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def load_libraries():
+    """The package with its libraries loaded.  ss.lib() and ss.tools_lib() first bring the in-tree build up to date under a lock file
+    in csrc/.  In a tree this user cannot write (a checkout that another user built) that raises PermissionError before anything is
+    checked; the libraries build() made are then loaded as they are.  A library that is missing is an error: build() first."""
+    import ctypes
+    import sliceslice_rs_amd as ss
+    try:
+        ss.lib()
+        ss.tools_lib()
+    except PermissionError as e:
+        b, s = sys.modules["sliceslice_rs_amd._build"], sys.modules["sliceslice_rs_amd.searcher"]
+        for path in (b.library_path(), b.tools_library_path()):
+            if not os.path.exists(path):
+                fail("%s is missing and the tree is not writable (%s): run build() first" % (path, e))
+        log("bench.py: %s; loading the libraries build() made as they are" % e)
+        if s._lib is None:
+            s._lib = s._load(os.environ.get("SLICESLICE_HIP_LIB") or b.library_path())
+        if s._tools is None:
+            s._tools = s._bind(ctypes.CDLL(b.tools_library_path(), mode=ctypes.RTLD_LOCAL), s.TOOLS_ABI, strict=True)
+    return ss
 
 
 def absent_needle(ss, n):
@@ -586,7 +620,11 @@ def native_measurements(ss, headline_gib=None):
     import subprocess
     out = {}
     try:
-        exe = sys.modules["sliceslice_rs_amd._build"].build_native_bench()
+        b = sys.modules["sliceslice_rs_amd._build"]
+        try:
+            exe = b.build_native_bench()
+        except PermissionError:
+            exe = b.native_bench_path()                    # a tree this user cannot write: the binary build() made
         gd = os.path.join(ROOT, "tests", "golden", "data")
         jobs = [("latency_us", [exe, "latency", "1000"]),
                 ("1", [exe, "config1", os.path.join(gd, "i386.txt"), os.path.join(gd, "words.txt"), "3"])]
@@ -638,7 +676,7 @@ def measure_traffic(gib=8.0, launches=6):
 
 def traffic_child(args):
     """--traffic-child: nothing but `steps` launches of the headline kernel (the parent counts their FETCH_SIZE)."""
-    import sliceslice_rs_amd as ss
+    ss = load_libraries()
     torch.cuda.set_device(0)
     n = int(args.haystack_gib * (1 << 30))
     hay = torch.empty(n, dtype=torch.uint8, device="cuda")
@@ -787,6 +825,58 @@ def write_line(real_stdout, out):
     os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
 
+def planted_cases(needle, total, cases=16):
+    """The fixed, seeded cases of --dump-outputs: (offset in the logical haystack, bytes planted there, expected answer).  The needle
+    goes in whole (true) or, in about half the cases, with one byte other than its 0xFF changed to another non-0xFF value (a near
+    miss: false, because the haystack holds no other 0xFF for an occurrence to line up with)."""
+    rng = np.random.default_rng(SEED_OUTPUTS)
+    n = len(needle)
+    others = [i for i in range(n) if needle[i] != 0xFF]
+    out = []
+    for _ in range(cases):
+        at = int(rng.integers(0, total - n + 1))
+        nd = bytearray(needle)
+        whole = not others or bool(rng.integers(0, 2))
+        if not whole:
+            j = others[int(rng.integers(0, len(others)))]
+            nd[j] = (nd[j] + 1) % 0xFF
+        out.append((at, bytes(nd), whole))
+    return out
+
+
+def planted_answers(search, shards, begins, needle, total):
+    """What --dump-outputs adds to the last step's answer: the timed call itself (`search`: the same handle on the same buffers) once
+    per planted case, after everything the line reports has been measured.  Every shard that holds part of a case gets its part; the
+    bytes are restored after each case."""
+    got = []
+    for at, nd, _ in planted_cases(needle, total):
+        saved = []
+        for t, b in zip(shards, begins):
+            lo, hi = max(at, b), min(at + len(nd), b + t.numel())
+            if lo < hi:
+                saved.append((t, lo - b, t[lo - b: hi - b].clone()))
+                t[lo - b: hi - b] = torch.tensor(list(nd[lo - at: hi - at]), dtype=torch.uint8, device=t.device)
+        for t, _, _ in saved:
+            torch.cuda.synchronize(t.device)
+        got.append(float(search()))
+        for t, i, old in saved:
+            t[i: i + old.numel()] = old
+            torch.cuda.synchronize(t.device)
+    return got
+
+
+def finish(real_stdout, out, dump_dir):
+    """--dump-outputs DIR first, then THE line.  `_outputs` holds what the timed path returned: `found`, its answer in the last timed
+    step, and `planted`, its answers to the planted cases.  A line that came from the single-process child (N > 1, --forms both) has
+    none, because the child wrote DIR itself."""
+    outputs = out.pop("_outputs", None)
+    if dump_dir and outputs is not None:
+        os.makedirs(dump_dir, exist_ok=True)
+        for name, values in outputs.items():
+            np.save(os.path.join(dump_dir, name + ".npy"), np.array(values, dtype=np.float32))
+    write_line(real_stdout, out)
+
+
 def librccl_fields(ss, native):
     """config.librccl_path / librccl_version of an N > 1 line: WHICH librccl the native communicator's ncclAllReduce lives in (dladdr)
     and its ncclGetVersion - a process with torch in it holds torch's bundled library next to the system's."""
@@ -821,8 +911,7 @@ def wg_histogram(seen):
 def run_single_process(args, why=None, share=False):
     """All `--gpus` devices from THIS process: ss_comm_init_all (ncclCommInitAll), one shard, one stream and one issue thread per
     device (ss_search_sharded_all).  Returns the line (a dict), `config.launcher` = "single-process"."""
-    import sliceslice_rs_amd as ss
-    ss.lib()
+    ss = load_libraries()
     G = args.gpus
     if torch.cuda.device_count() < G and not share:
         fail("--gpus %d but only %d HIP device(s) visible" % (G, torch.cuda.device_count()))
@@ -846,9 +935,10 @@ def run_single_process(args, why=None, share=False):
         fail("RCCL reports %r ranks for the set, expected %d" % (rccl_ranks, G))
     if os.environ.get("SLICESLICE_SET_THREADS") == "0":
         transport = transport.replace("one issue thread per device, each with its own ncclAllReduce", "issued from one thread, the all-reduces as one group")
-    shards = []
+    shards, begins = [], []
     for g in range(G):
         b, e = node.shard_range(total, g)
+        begins.append(b)
         with torch.cuda.device(devices[g]):
             t = torch.empty(e - b, dtype=torch.uint8, device="cuda:%d" % devices[g])
             ss.fill_random_device(t, SEED_HAY, b)
@@ -880,14 +970,19 @@ def run_single_process(args, why=None, share=False):
     assert found is False
     value = total * args.steps / elapsed / 1e9
     ms_per_step = elapsed / args.steps * 1e3
-    # what a search costs besides its scan: the same call on 4 MiB shards (launches + collective + answer words)
-    small = [t[: 4 << 20] for t in shards]
-    for _ in range(20):
-        node.search_in(small)
-    t1 = time.perf_counter()
-    for _ in range(100):
-        node.search_in(small)
-    small_us = (time.perf_counter() - t1) / 100 * 1e6
+    small_shard = {}
+    if args.full:
+        # what a search costs besides its scan: the same call on 4 MiB shards (launches + collective + answer words)
+        small = [t[: 4 << 20] for t in shards]
+        for _ in range(20):
+            node.search_in(small)
+        t1 = time.perf_counter()
+        for _ in range(100):
+            node.search_in(small)
+        small_us = (time.perf_counter() - t1) / 100 * 1e6
+        small_shard = dict(small_shard_call_us=round(small_us, 1),
+                           note="small_shard_call_us: the same call on 4 MiB shards (launches + collective + answer words; ~1 us of scan)")
+        del small
     iss = np.median(np.array(issue), axis=0)
     ratio, src = stored_traffic()
     shard_bytes = max(t.numel() for t in shards)
@@ -904,17 +999,19 @@ def run_single_process(args, why=None, share=False):
                                   waited_for_free_vram_s=round(waited_s, 2), vram_used_at_start=used_at_start,
                                   workgroups_per_cu_timed=wg_histogram(wgs)),
         "roofline": roofline_block(shard_bytes, per_dev[slowest], value, G, ratio, src),
-        "step_breakdown": step_breakdown(ms_per_step, per_dev, small_shard_call_us=round(small_us, 1),
+        "step_breakdown": step_breakdown(ms_per_step, per_dev,
                                          issue_us={"scans": round(float(iss[0]), 1), "collective": round(float(iss[1]), 1),
                                                    "answer_words": round(float(iss[2]), 1), "all": round(float(iss[3]), 1),
                                                    "note": "host time of ss_search_sharded_all's issue phase, median over the timed steps: per-device "
                                                            "maxima when every device has its own issue thread, sums when one thread issues everything"},
-                                         note="small_shard_call_us: the same call on 4 MiB shards (launches + collective + answer words; ~1 us of scan)"),
+                                         **small_shard),
     }
     out["roofline"]["per_rank"] = rank_stats(per_dev)
     out["roofline"]["kernel_ms_of"] = "device %d of the set, the slowest by median" % slowest
+    if args.dump_outputs:
+        out["_outputs"] = {"found": [found], "planted": planted_answers(lambda: node.search_in(shards), shards, begins, needle, total)}
     node.close()
-    del shards, small
+    del shards
     torch.cuda.empty_cache()
     return out
 
@@ -932,12 +1029,11 @@ def other_form_summary(o):
 def run_multi_process(args, ctx):
     """One rank per GPU (or the plain N = 1 run): every rank scans its shard and - N > 1 - joins ONE all-reduce per search
     (ss_search_sharded, native RCCL).  Rank 0 returns the line (a dict), the other ranks None."""
-    import sliceslice_rs_amd as ss
     dist, backend, world, rank, local_rank, share = ctx["dist"], ctx["backend"], ctx["world"], ctx["rank"], ctx["local_rank"], ctx["share"]
     transport = args.transport
     if share and world > 1 and transport == "rccl" and not os.environ.get("SLICESLICE_RCCL_LIB"):
         transport = "torch"                                    # RCCL refuses two ranks on one device (a stand-in named by SLICESLICE_RCCL_LIB does not)
-    ss.lib()
+    ss = load_libraries()
     info = ss.device_info()
     dev = "cuda" if backend == "nccl" else "cpu"
 
@@ -1027,10 +1123,12 @@ def run_multi_process(args, ctx):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        # every rank's kernel times, and what a sharded search costs besides its scan: the same collective call on a 4 MiB shard
-        # (launch + ~1 us of scan + all-reduce + answer word) next to the plain, rank-local call on the same bytes
+        # every rank's kernel times
         per_rank = [None] * world
         dist.all_gather_object(per_rank, [float(x) for x in kernel_ms])
+    if dist is not None and args.full:
+        # what a sharded search costs besides its scan: the same collective call on a 4 MiB shard (launch + ~1 us of scan +
+        # all-reduce + answer word) next to the plain, rank-local call on the same bytes
         small = shard[: 4 << 20]
         for _ in range(20):
             searcher.search_in(small)
@@ -1055,7 +1153,7 @@ def run_multi_process(args, ctx):
                                     "collective_only_us is their difference")
 
     ceiling = None
-    if not args.no_ceiling and rank == 0:
+    if args.full and not args.no_ceiling and rank == 0:
         ceiling = ss.read_ceiling_gbps(shard[: (shard.numel() // 16) * 16], reps=5)
 
     out = None
@@ -1094,7 +1192,12 @@ def run_multi_process(args, ctx):
                 out["roofline"]["placement_note"] = ("the scan kernel reached only %.3f of this buffer's plain-read rate (normally 0.975-0.992): "
                                                      "the haystack was allocated while the driver was still reclaiming another process's memory"
                                                      % (out["roofline"]["achieved"] / ceiling))
-        if world == 1 and not args.no_configs:
+    if args.dump_outputs:
+        planted = planted_answers(lambda: searcher.search_in(shard), [shard], [begin], needle, total)
+        if rank == 0:
+            out["_outputs"] = {"found": [found], "planted": planted}
+    if rank == 0:
+        if world == 1 and args.full and not args.no_configs:
             cfg = other_configs(ss, shard)
             room = torch.cuda.mem_get_info()[0] > total + (8 << 30)          # a second haystack of the same size fits
             cfg.update(native_measurements(ss, total / (1 << 30) if room else None))
@@ -1107,7 +1210,7 @@ def run_multi_process(args, ctx):
                            "latency_us and headline_native (the headline workload once more, in a process without Python or torch): "
                            "tools/native_bench (C ABI only)")
             out["configs"] = cfg
-        if world == 1:
+        if world == 1 and args.full:
             del shard
             torch.cuda.empty_cache()
             if not args.no_traffic:
@@ -1148,7 +1251,13 @@ def main():
     ap.add_argument("--cpu-sample-mib", type=int, default=1024)
     ap.add_argument("--no-ceiling", action="store_true",
                     help="skip the plain streaming-read ceiling (roofline.read_ceiling_gbps; a few launches, untimed)")
-    ap.add_argument("--ceiling", action="store_true", help="(default now) kept for compatibility")
+    ap.add_argument("--ceiling", action="store_true", help="(the default of --full) kept for compatibility")
+    ap.add_argument("--full", action="store_true",
+                    help="measure every untimed extra as well: read ceiling, live traffic pass, other configs, CPU baseline, "
+                         "small-shard calls (the --no-* options switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned to DIR/found.npy (the last timed step) and DIR/planted.npy (seeded "
+                         "planted cases, after the measurements), float32")
     ap.add_argument("--no-configs", action="store_true", help="skip the configs 1/3/5 + latency block (N = 1 only, untimed)")
     ap.add_argument("--no-traffic", action="store_true",
                     help="skip the live `rocprofv3 --pmc FETCH_SIZE` pass (N = 1 only, untimed); roofline.traffic then uses the stored ratio")
@@ -1160,6 +1269,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         fail("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        fail("--steps must be >= 1 and --warmup >= 0")
     if args.single_process:
         args.forms = "single"
     if args.cpu_report:
@@ -1185,7 +1296,7 @@ def main():
             return                                             # under a launcher: rank 0 drives every device, the others have nothing to do
         if not torch.cuda.is_available():
             fail("needs a GPU: the scan has no CPU path")
-        write_line(real_stdout, run_single_process(args, fallback_why, share))
+        finish(real_stdout, run_single_process(args, fallback_why, share), args.dump_outputs)
         return
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1231,8 +1342,8 @@ def main():
             log("bench.py: rank %d: torch.distributed bootstrap failed (%r)" % (rank, e))
             if rank != 0 or share:
                 raise SystemExit(0 if not share else 1)
-            write_line(real_stdout, run_single_process(args, "torch.distributed bootstrap failed on rank 0 (%s); every device driven from rank 0's "
-                                                             "process instead" % (repr(e)[:200],)))
+            finish(real_stdout, run_single_process(args, "torch.distributed bootstrap failed on rank 0 (%s); every device driven from rank 0's "
+                                                         "process instead" % (repr(e)[:200],)), args.dump_outputs)
             return
 
     ctx = dict(dist=dist, backend=backend, world=world, rank=rank, local_rank=local_rank, share=share)
@@ -1248,6 +1359,7 @@ def main():
             cmd = [sys.executable, os.path.abspath(__file__), "--forms", "single", "--gpus", str(args.gpus), "--steps", str(args.steps),
                    "--warmup", str(args.warmup), "--haystack-gib", "%g" % args.haystack_gib, "--needle-len", str(args.needle_len),
                    "--settle-seconds", "%g" % args.settle_seconds, "--variant", str(args.variant), "--grid", str(args.grid)]
+            cmd += (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK",
                                                                       "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
             try:
@@ -1268,7 +1380,7 @@ def main():
                                            "barrier); this line is the better of the two")
             out = best
     if rank == 0:
-        write_line(real_stdout, out)
+        finish(real_stdout, out, args.dump_outputs)
     if dist is not None:
         dist.barrier(group=cpu_group) if cpu_group is not None else dist.barrier()
         dist.destroy_process_group()

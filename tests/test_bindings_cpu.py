@@ -155,9 +155,33 @@ def test_bench_refuses_to_mislabel_a_run():
     out = _bench(["--gpus", "4", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert out.returncode != 0 and out.stdout.strip() == ""
     assert "WORLD_SIZE=2 but --gpus 4" in out.stderr
+    out = _bench(["--steps", "0", "--warmup", "0"])
+    assert out.returncode != 0 and out.stdout.strip() == "" and "--steps must be >= 1" in out.stderr
     if not torch.cuda.is_available():
         out = _bench(["--steps", "1", "--warmup", "0"])
         assert out.returncode != 0 and out.stdout.strip() == "" and "no CPU path" in out.stderr
+
+
+def test_bench_loads_the_built_libraries_from_a_tree_it_cannot_write():
+    """bench.py may run as a user who cannot write the checkout another user built: the build lock in csrc/ then raises
+    PermissionError before anything is checked, and bench.py loads the libraries build() made instead of failing."""
+    code = ("import importlib.util, sys\n"
+            "sys.path.insert(0, %r)\n"
+            "import sliceslice_rs_amd\n"
+            "from oracle import oracle as O\n"
+            "def refuse(self):\n"
+            "    raise PermissionError(13, 'Permission denied', self._path)\n"
+            "sys.modules['sliceslice_rs_amd._build']._Lock.__enter__ = refuse\n"
+            "spec = importlib.util.spec_from_file_location('bench_under_test', %r)\n"
+            "bench = importlib.util.module_from_spec(spec)\n"
+            "spec.loader.exec_module(bench)\n"
+            "ss = bench.load_libraries()\n"
+            "assert (ss.fill_random_host(4096, 7) == O.fill_random(4096, 7)).all()\n"
+            "assert ss.choose_filter_triple(b'privilege level') == ss.choose_filter_triple(b'privilege level', None)\n"
+            "print('loaded')\n") % (ROOT, os.path.join(ROOT, "bench.py"))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0 and out.stdout.strip() == "loaded", out.stdout[-2000:] + out.stderr[-3000:]
+    assert "loading the libraries build() made as they are" in out.stderr
 
 
 def test_filter_pair_choice_properties():

@@ -219,9 +219,9 @@ def test_bench_single_process_mode_and_the_fallback_to_it():
 
 
 def test_live_bench_line_contract_and_measured_traffic():
-    """The line as the driver gets it (smaller haystack, same code path): every contract field, the roofline block's arithmetic, and
+    """The line of a --full run (smaller haystack, same code path): every contract field, the roofline block's arithmetic, and
     roofline.traffic MEASURED in the run (a child `rocprofv3 --pmc FETCH_SIZE` pass) rather than a stored ratio."""
-    d = _line(_run_bench(["--haystack-gib", "4", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-configs"], {}, timeout=1200))
+    d = _line(_run_bench(["--full", "--haystack-gib", "4", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-configs"], {}, timeout=1200))
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str),
                      ("data", str), ("config", dict), ("roofline", dict)):
@@ -232,6 +232,26 @@ def test_live_bench_line_contract_and_measured_traffic():
     assert r["traffic_source"].startswith("measured in this run"), r.get("traffic_note") or r["traffic_source"]
     assert 0.99 <= r["traffic_per_algorithmic_byte"] <= 1.05, r["traffic_per_algorithmic_byte"]
     assert abs(r["traffic"] - r["traffic_per_algorithmic_byte"] * r["algorithmic_bytes_per_launch"]) < 1e-3 * r["traffic"]
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_answers(tmp_path):
+    """Without --full the run sets up, warms up, times --steps steps and prints the line: no read ceiling, other configs, CPU baseline
+    or live traffic pass.  --dump-outputs DIR holds what search_in returned in the last timed step (the needle is absent) and its
+    answers to the seeded planted cases: true where the needle went in whole, false for the near misses."""
+    import importlib.util
+    import numpy as np
+    import sliceslice_rs_amd as ss
+    d = _line(_run_bench(["--haystack-gib", "2", "--steps", "7", "--warmup", "1", "--dump-outputs", str(tmp_path)], {}))
+    assert d["steps"] == 7 and d["roofline"]["kernel_launches"] == 7 and d["ms_per_step"] > 0 and d["value"] > 1000
+    assert not {"cpu_baseline", "configs", "configs_summary"} & set(d) and "read_ceiling_gbps" not in d["roofline"]
+    assert d["roofline"]["traffic_source"].startswith("stored ratio")
+    found, planted = np.load(tmp_path / "found.npy"), np.load(tmp_path / "planted.npy")
+    assert found.dtype == planted.dtype == np.float32 and found.tolist() == [0.0]
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    want = [float(c[2]) for c in bench.planted_cases(bench.absent_needle(ss, 16), d["config"]["haystack_bytes"])]
+    assert planted.tolist() == want and 0.0 in want and 1.0 in want, (planted.tolist(), want)
 
 
 # ---- the NATIVE collective code with more than one rank, on one GPU ----------------------------------------------------------
@@ -345,7 +365,7 @@ def test_bench_with_eight_ranks_on_the_native_transport():
     import json
     env, _ = _fake_env({"SS_BENCH_SHARE_GPU": "1", "SS_BENCH_BACKEND": "gloo"})
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
-                          "--haystack-gib", "2", "--no-ceiling"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                          "--haystack-gib", "2", "--no-ceiling", "--full"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout
