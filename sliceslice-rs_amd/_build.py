@@ -3,6 +3,8 @@
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_service.so  the product's objects plus the resident search service (include/sliceslice_hip_service.h): an
                                   opt-in component outside the hot path - a process uses one library or the other
+    libsliceslice_hip_matches.so  the product's objects plus the all-matches scan (include/sliceslice_hip_matches.h: count and
+                                  find-all): opt-in like the service - a process uses one library or the other
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
     libsliceslice_hip_tuning.so   the product's sources with -DSS_TUNING_VARIANTS -DSS_TEST_HOOKS: every kernel variant,
                                   ss_searcher_set_variant / _set_grid, fault injection (tools/, the variant and hook tests)
@@ -28,9 +30,11 @@ _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_CSRC, "libsliceslice_hip.so")
 _TOOLS_SO = os.path.join(_CSRC, "libsliceslice_hip_tools.so")
 _SERVICE_SO = os.path.join(_CSRC, "libsliceslice_hip_service.so")
+_MATCHES_SO = os.path.join(_CSRC, "libsliceslice_hip_matches.so")
 # host-side translation units (ss_internal.hpp lists what each holds) ...
 _HOST_SOURCES = ["ss_core.hip", "ss_scan.hip", "ss_census.hip", "ss_host.hip", "ss_batched.hip", "ss_comm.hip"]
 _SERVICE_SOURCES = ["ss_service.hip"]       # NOT in the product: libsliceslice_hip_service.so and the hooks builds
+_MATCHES_SOURCES = ["ss_matches.hip", "scan_inst_all.hip"]     # NOT in the product: libsliceslice_hip_matches.so only
 # ... and the scan kernel family, one explicit-instantiation unit per (U, load flavour, search / find).  The product holds what
 # the constructors and ss_searcher_set_filter3 can select (scan_launch.hpp::kernel_built): U = 4, non-temporal loads.
 _KERNEL_SOURCES = ["scan_inst_u4_nt1.hip", "scan_inst_find_nt1.hip"]
@@ -38,7 +42,8 @@ _SOURCES = _HOST_SOURCES + _KERNEL_SOURCES
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
 _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
-            "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            "matches_launch.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_service.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_tuning.h")]
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden"]
@@ -63,6 +68,14 @@ def tools_library_path():
 
 def service_library_path():
     return _SERVICE_SO
+
+
+def matches_library_path():
+    return _MATCHES_SO
+
+
+def matches_resources_path():
+    return _MATCHES_RESOURCES
 
 
 def native_bench_path():
@@ -105,9 +118,12 @@ def _run(cmd, verbose):
     subprocess.check_call(cmd)
 
 
-def _build_variant(so, obj_suffix, extra_flags, link_flags, force, verbose, sources, own=None, record_resources=False):
+def _build_variant(so, obj_suffix, extra_flags, link_flags, force, verbose, sources, own=None, record_resources=False,
+                   resources=None):
     """Compiles `sources` (those in `own` - default: all - with `extra_flags` into <name><obj_suffix>; the others are taken as the
-    regular build's <name>.o) and links them into `so`."""
+    regular build's <name>.o) and links them into `so`.  record_resources: every kernel's registers of the library go to
+    `resources` (default csrc/kernel_resources.json)."""
+    resources = resources or _RESOURCES
     own = sources if own is None else own
     newest_header = max(_mtime(h) for h in _HEADERS)
     objs = [os.path.join(_CSRC, s[:-4] + (obj_suffix if s in own else ".o")) for s in sources]
@@ -119,7 +135,7 @@ def _build_variant(so, obj_suffix, extra_flags, link_flags, force, verbose, sour
         if force or stale or not os.path.exists(obj) or os.path.getmtime(obj) < max(_mtime(src), newest_header):
             todo.append((src, obj))
     if (not todo and os.path.exists(so) and os.path.getmtime(so) >= max(os.path.getmtime(o) for o in objs) and
-            (not record_resources or os.path.exists(_RESOURCES))):
+            (not record_resources or os.path.exists(resources))):
         return so
     hipcc = _hipcc()
     tag = ".tmp%d" % os.getpid()
@@ -154,13 +170,14 @@ def _build_variant(so, obj_suffix, extra_flags, link_flags, force, verbose, sour
         for o in objs:
             if os.path.exists(o + ".res"):
                 rows += json.load(open(o + ".res"))
-        with open(_RESOURCES + tag, "w") as f:
+        with open(resources + tag, "w") as f:
             json.dump(rows, f, indent=0)
-        os.replace(_RESOURCES + tag, _RESOURCES)
+        os.replace(resources + tag, resources)
     return so
 
 
 _RESOURCES = os.path.join(_CSRC, "kernel_resources.json")
+_MATCHES_RESOURCES = os.path.join(_CSRC, "kernel_resources_matches.json")
 _RES_KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
              "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills",
              "LDS Size [bytes/block]": "lds_bytes"}
@@ -211,6 +228,21 @@ def build_service(force=False, verbose=False):
     build(verbose=verbose)                                  # the product's objects are shared
     with _Lock(".build_service.lock"):
         return _build_variant(_SERVICE_SO, ".o", [], [], force, verbose, _SOURCES + _SERVICE_SOURCES, own=_SERVICE_SOURCES)
+
+
+def build_matches(force=False, verbose=False):
+    """The product's objects + the all-matches scan (csrc/ss_matches.hip, scan_inst_all.hip) -> csrc/libsliceslice_hip_matches.so
+    (include/sliceslice_hip_matches.h).  The library's kernels are recorded in csrc/kernel_resources_matches.json."""
+    build(verbose=verbose)                                  # the product's objects (and their resource records) are shared
+    with _Lock(".build_matches.lock"):
+        return _build_variant(_MATCHES_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES, own=_MATCHES_SOURCES,
+                              record_resources=True, resources=_MATCHES_RESOURCES)
+
+
+def matches_kernel_resources():
+    """Rows of csrc/kernel_resources_matches.json (written by build_matches()): the product's kernels and the all-matches ones."""
+    build_matches()
+    return json.load(open(_MATCHES_RESOURCES))
 
 
 def build_tools(force=False, verbose=False):

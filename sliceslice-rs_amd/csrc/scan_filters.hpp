@@ -531,9 +531,11 @@ struct VerifyArgs {
     uint64_t n, end;
 };
 
-template <bool ONE_BYTE>
-__device__ __forceinline__ bool verify_flags(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
-                                             const uint8_t *s_needle, uint64_t &where, uint64_t far_off = 0)
+// ALL (the all-matches kernels, scan_tiles<..., ALL = true>): no early exit - every flagged offset is verified, and bit 4j+t of
+// *mask is set for each match at byte 4j+t of the chunk (address order).  The range rule is the same.
+template <bool ONE_BYTE, bool ALL = false>
+__device__ __forceinline__ bool verify_flags_walk(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
+                                                  const uint8_t *s_needle, uint64_t &where, uint64_t far_off, uint32_t *mask)
 {
     bool hit = false;
     // all 16 flags of the lane in one word: flag of byte 4j+t at bit 8t+j (bit 7 of byte t of g[j] >> (7-j))
@@ -541,9 +543,9 @@ __device__ __forceinline__ bool verify_flags(const uint32_t g[4], uint64_t chunk
                  ((g[3] & 0x80808080u) >> 4);
     // address order = j major, t minor: take dword 0's flags first (bits 0, 8, 16, 24), then dword 1's ...
 #pragma unroll 1
-    for (int j = 0; j < 4 && !hit; ++j) {
+    for (int j = 0; j < 4 && (ALL || !hit); ++j) {
         uint32_t mj = (m >> j) & 0x01010101u;
-        while (mj != 0 && !hit) {
+        while (mj != 0 && (ALL || !hit)) {
             const int bit = __ffs((int)mj) - 1;         // lowest flagged byte first (tzcnt, lib.rs:221)
             mj &= mj - 1;                               // clear lowest set bit        (lib.rs:247)
             const uint64_t a = chunk * 16 + (uint64_t)(j * 4 + (bit >> 3));
@@ -553,10 +555,31 @@ __device__ __forceinline__ bool verify_flags(const uint32_t g[4], uint64_t chunk
                 else if (far_off != 0 && va.hay[i + far_off] != va.needle[far_off]) hit = false;   // the caller's far filter byte
                 else hit = verify_candidate(va.hay, va.needle, va.n, s_needle, i);
                 where = i;                              // lowest match of this lane when hit
+                if constexpr (ALL) {
+                    if (hit) *mask |= 1u << (j * 4 + (bit >> 3));
+                }
             }
         }
     }
     return hit;
+}
+
+template <bool ONE_BYTE>
+__device__ __forceinline__ bool verify_flags(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
+                                             const uint8_t *s_needle, uint64_t &where, uint64_t far_off = 0)
+{
+    return verify_flags_walk<ONE_BYTE, false>(g, chunk, pr, va, s_needle, where, far_off, nullptr);
+}
+
+// Every match among the lane's flags: bit k set <=> hay[chunk * 16 - mis + k ..) holds the needle (k < 16).
+template <bool ONE_BYTE>
+__device__ __forceinline__ uint32_t verify_flags_all(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
+                                                     const uint8_t *s_needle, uint64_t far_off)
+{
+    uint64_t where = 0;
+    uint32_t mask = 0;
+    (void)verify_flags_walk<ONE_BYTE, true>(g, chunk, pr, va, s_needle, where, far_off, &mask);
+    return mask;
 }
 
 // movemask of one flag dword: bit 7 of byte t -> bit t
@@ -639,6 +662,71 @@ __device__ __forceinline__ bool exact_verify_piece(const u32x4 &A, const NextPie
         where_off = off;                                // lowest match of this lane when hit: index ubase + off
     }
     return hit;
+}
+
+// Companion of exact_verify_piece for the all-matches kernels (kept apart so that the find / search kernels' code stays what it is):
+// every flag is settled, no early exit, and the result is the lane's match mask - bit t set <=> a match at window byte t, i.e. at
+// hay index chunk_wave * 16 - mis + 16 * lane + t: the lane's own offsets at bits 0..15, those handed over from the next lane at
+// bits 16 + t.  A flag is handed to ONE lane, so every offset is owned by exactly one lane.  Same range rule.
+__device__ __forceinline__ uint32_t exact_verify_piece_all(const u32x4 &A, const NextPiece &np, const uint32_t g[4], uint64_t chunk_wave,
+                                                           int lane, const Problem &pr, const VerifyArgs &va, const uint32_t cmp16[4],
+                                                           uint32_t exact)
+{
+    // index of the needle's first byte for a candidate at stream byte t of this lane's window: ubase (wave-uniform; wraps for
+    // chunks in front of the haystack) + 16 * lane + t
+    const uint64_t ubase = chunk_wave * 16 - pr.mis;
+    const uint8_t *hb = va.hay + ubase;
+    const uint32_t exact_len = exact & 0xFFu, back = (exact >> 8) & 0xFFu;          // wave-uniform
+    // (named scalars, not an array: a select between array ELEMENTS becomes a select between addresses, and the window
+    // ends up in scratch memory behind a dynamic index)
+    auto hop = [&](uint32_t nword, uint32_t own) {
+        return from_next_lane_or(np.kind == 1 ? rotate_from_next_lane(nword) : nword, own);
+    };
+    const uint32_t w0 = A.x, w1 = A.y, w2 = A.z, w3 = A.w;
+    const uint32_t w4 = hop(np.N.x, w0), w5 = hop(np.N.y, w1), w6 = hop(np.N.z, w2), w7 = hop(np.N.w, w3);
+    uint32_t M[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int rem = (int)exact_len - 4 * j;
+        M[j] = rem >= 4 ? ~0u : (rem <= 0 ? 0u : (1u << (8 * rem)) - 1u);
+    }
+    // bit t: a candidate whose first filter byte is stream byte t of {own chunk, next lane's chunk}
+    uint32_t flags = flag_nibble(g[0]) | (flag_nibble(g[1]) << 4) | (flag_nibble(g[2]) << 8) | (flag_nibble(g[3]) << 12);
+    if (back != 0) {
+        const uint32_t low = flags & ((1u << back) - 1u);
+        flags = (lane == 0 ? flags : flags & ~low) | (from_next_lane_or(0u, low) << 16);
+    }
+    const uint64_t anchor = (uint64_t)((pr.base + pr.mis) - va.hay);     // index of the first filter byte in the needle
+    const uint32_t front = (uint32_t)(anchor - back);                    // needle bytes in front of the register window
+    uint32_t mask = 0;
+    while (flags != 0) {
+        const int t = __ffs((int)flags) - 1;            // lowest flagged byte first (tzcnt, lib.rs:221)
+        flags &= flags - 1;                             // clear lowest set bit        (lib.rs:247)
+        const uint32_t off = 16u * (uint32_t)lane + (uint32_t)t;
+        const uint64_t i = ubase + off;                 // wraps for bytes in front of the haystack
+        if (i >= va.end) continue;
+        uint32_t in_memory = front;                     // needle bytes this candidate still has to match in memory
+        if ((uint32_t)t < back) {
+            // lane 0: the bytes in front of this candidate lie in a chunk the wave may not hold - the whole needle, in memory
+            in_memory = (uint32_t)va.n;
+        } else {
+            const int start = t - (int)back;            // byte offset of needle[first - back] in the window: 0 .. 15
+            const int q = start >> 2;
+            const uint32_t r = (uint32_t)(start & 3);
+            auto pick = [&](uint32_t a, uint32_t b1, uint32_t c, uint32_t d) {
+                const uint32_t lo = q & 1 ? b1 : a, hi = q & 1 ? d : c;
+                return q & 2 ? hi : lo;
+            };
+            const uint32_t sw[5] = {pick(w0, w1, w2, w3), pick(w1, w2, w3, w4), pick(w2, w3, w4, w5), pick(w3, w4, w5, w6),
+                                    pick(w4, w5, w6, w7)};
+            uint32_t diff = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) diff |= (__builtin_amdgcn_alignbyte(sw[j + 1], sw[j], r) ^ cmp16[j]) & M[j];
+            if (diff != 0) continue;
+        }
+        if (in_memory == 0 || same_bytes(hb, off, va.needle, in_memory)) mask |= 1u << t;
+    }
+    return mask;
 }
 
 // tells the compiler that a 64-bit value is wave-uniform (SGPR pair)

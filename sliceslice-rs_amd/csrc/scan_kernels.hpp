@@ -78,12 +78,50 @@ template <bool BATCHED> constexpr bool kNoForget = BATCHED;
 // problem counts it into the plan's tally.
 template <class T, class = void> struct SingleLaunchPlan : std::false_type {};
 template <class T> struct SingleLaunchPlan<T, std::void_t<decltype(T::kSingleLaunchPlan)>> : std::bool_constant<T::kSingleLaunchPlan> {};
+// ALL (scan_all_kernel only): every match, no early exit.  `sink` is the launch's AllTiles.  There are no flag polls; every candidate of
+// every piece is verified (verify_flags_all / exact_verify_piece_all return a lane's full match mask), and each matching offset belongs
+// to exactly one (wave, piece, lane) - pieces do not overlap, and the exact compare hands a flag to ONE neighbour.  Count launches add
+// the masks' popcounts per lane; emit launches keep the tile's masks and write the offsets in address order once every wave of the
+// workgroup has told the others (LDS) how many it holds in the tile.
+struct AllTiles {
+    uint32_t lane_count;      // count launches: this lane's matches so far
+    bool emit;                // wave-uniform: write offsets instead of counting
+    uint64_t rank;            // emit: rank of the workgroup's next match among all matches of the haystack (workgroup-uniform)
+    uint64_t *out;            // emit: the caller's offsets; ranks >= capacity are not written
+    uint64_t capacity;
+    uint32_t *s_wave;         // LDS: one count per wave of the workgroup
+};
+
+// sum of v over the wave, in every lane: DPP within rows of 16, then the four rows' sums
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140 /* row_mirror */, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// sum of v over the lanes below this one (emit launches only: tiles that hold matches)
+__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t v, int lane)
+{
+    uint32_t x = v;
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)x, (unsigned)k, kWave);
+        if (lane >= k) x += y;
+    }
+    return x - v;
+}
+
 template <int Q, int MODE, bool ONE_BYTE, int U, int NTMODE, bool FIND = false, bool L8 = false, bool LAZY_ORDER = false,
-          typename ColdT = ColdInRegisters>
+          typename ColdT = ColdInRegisters, bool ALL = false>
 __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_t *s_needle_block, uint64_t tile0,
                                            uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr)
 {
     static_assert(!L8 || (MODE == 0 && !FIND), "the 8-byte layout covers the single-stream bool kernels");
+    static_assert(!ALL || (!FIND && !L8 && !LAZY_ORDER), "the all-matches mode has kernels of its own (scan_all_kernel)");
     static_assert(Q != kQDynamic || (MODE == 0 && !L8), "a run-time window is for the single-stream kernels' three-byte phase");
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "single-stream kernels only");
     constexpr bool SHIFTED = MODE >= 2;
@@ -123,8 +161,57 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     uint32_t exact_len = 0u;
     bool dense = false;                                                     // L8: the previous tile had candidates
     const int d = (int)pr.d;                                                // SHIFTED: 1 <= d <= 62
+    // ALL: the match masks of the wave's pieces in the current tile (emit launches), and what happens at the end of every tile
+    AllTiles *all = static_cast<AllTiles *>(sink);
+    uint32_t all_mask[U];
+    auto tile_done = [&](uint64_t tile) {
+        if constexpr (ALL) {
+            if (all->emit) {
+                uint32_t c = 0;
+#pragma unroll
+                for (int u = 0; u < U; ++u) c += (uint32_t)__builtin_popcount(all_mask[u]);
+                const uint32_t wc = wave_sum(c);
+                if (lane == 0) all->s_wave[wave] = wc;
+                __syncthreads();
+                uint32_t before = 0, total = 0;                 // matches of the waves in front of this one, of the whole tile
+                for (int w = 0; w < wpb; ++w) {
+                    const uint32_t v = all->s_wave[w];
+                    before += w < wave ? v : 0u;
+                    total += v;
+                }
+                __syncthreads();                                // (the next tile rewrites s_wave)
+                if (wc != 0) {
+                    const uint64_t chunk0 = (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64;
+                    uint64_t r = all->rank + before;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const uint32_t pc = (uint32_t)__builtin_popcount(all_mask[u]);
+                        const uint32_t ex = wave_exclusive_sum(pc, lane);
+                        uint64_t rr = r + ex;
+                        uint32_t m = all_mask[u];
+                        const uint64_t ibase = (chunk0 + 64 * u + lane) * 16 - pr.mis;     // offset of mask bit 0
+                        while (m != 0 && rr < all->capacity) {
+                            const int bit = __ffs((int)m) - 1;              // lowest first: address order within the lane
+                            m &= m - 1;
+                            all->out[rr++] = ibase + (uint64_t)bit;
+                        }
+                        r += (uint32_t)__builtin_amdgcn_readlane((int)(ex + pc), kWave - 1);
+                    }
+                }
+                all->rank += total;
+            }
+        } else {
+            (void)tile;
+        }
+    };
 
-    for (uint64_t tile = tile0; tile < tile_end; tile += tile_step) {
+    for (uint64_t tile = tile0; tile < tile_end; tile_done(tile), tile += tile_step) {
+        if constexpr (ALL) {
+            if (all->emit) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) all_mask[u] = 0;
+            }
+        }
         u32x4 A[U], H = {0, 0, 0, 0};
         const uint64_t chunk0 = (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64;   // wave-uniform
         // FIND polls first (oldest load, so waiting for it does not drain the data loads behind it); the value
@@ -217,7 +304,7 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                 }
             }
             // the poll is issued behind the data loads and consumed after them
-            stop = FIND ? 0 : poll_found(found, pr.epoch);
+            stop = FIND || ALL ? 0 : poll_found(found, pr.epoch);
             if (FIND) best_now = uniform64(best_raw);
 
             // ---- phase 1: the two-byte filter for all U pieces, straight-line (loads are consumed in order) ----
@@ -506,6 +593,23 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
 #ifdef SS_CAND_PROF
                 prof_refine += prof_p1 - prof_p0;
 #endif
+                if constexpr (ALL) {
+                    // every match of the piece, no early exit
+                    uint32_t mk;
+                    if (EXACT_OK && exact_len != 0) {
+                        NextPiece np;
+                        np.N = u + 1 < U ? A[u + 1] : H;
+                        np.kind = u + 1 < U ? 1 : 0;
+                        mk = exact_verify_piece_all(A[u], np, g, chunk0 + 64 * u, lane, pr, va, tail16, exact_len);
+                    } else {
+                        stage_once();
+                        const uint64_t far_off = MODE == 0 && !ONE_BYTE ? uniform64(cold()->far_off) : 0;
+                        mk = verify_flags_all<ONE_BYTE>(g, chunk0 + 64 * u + lane, pr, va, s_needle, far_off);
+                    }
+                    if (all->emit) all_mask[u] = mk;
+                    else all->lane_count += (uint32_t)__builtin_popcount(mk);
+                    continue;
+                }
                 uint64_t where = 0;
                 bool h;
                 if (EXACT_OK && exact_len != 0) {               // wave-uniform: the needle's dwords are at hand
@@ -569,7 +673,7 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                     }
                 }
             }
-            if (!FIND) {
+            if (!FIND && !ALL) {
                 const uint64_t hits = __ballot(hit);
                 if (hits != 0) {
                     // ONE lane of the wave publishes, and only the wave that flips the device flag writes the
@@ -734,6 +838,52 @@ __global__ void SS_SCAN_OCCUPANCY __launch_bounds__(kMaxBlock) scan_kernel(const
                 __hip_atomic_store(c->host_done, hit ? (long long)(off + 1) : -1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
+    }
+}
+
+// ---- all matches: count / per-workgroup count / emit (libsliceslice_hip_matches.so: ss_matches.hip, scan_inst_all.hip) ----------
+struct AllArgs {
+    uint64_t *total;            // kAllCount: the haystack's count (one device-scope add per workgroup that has matches)
+    uint32_t *wg_count;         // kAllCountPerWorkgroup: written, one per workgroup (zero included); kAllEmit: read
+    const uint64_t *wg_rank;    // kAllEmit: exclusive prefix sum of wg_count
+    uint64_t *out;              // kAllEmit: offsets, ranks below capacity only
+    uint64_t capacity;
+    uint32_t mode;
+};
+constexpr uint32_t kAllCount = 0, kAllCountPerWorkgroup = 1, kAllEmit = 2;
+
+// Contiguous tiles per workgroup (tiles_per_block >= 1), so that workgroup order is address order.  No entry peek, no flag poll.
+template <int Q, int MODE, bool ONE_BYTE>
+__global__ void __launch_bounds__(kMaxBlock) scan_all_kernel(const Problem pr, AllArgs aa, uint64_t tiles_per_block)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_needle[];
+    __shared__ uint32_t s_wave[kMaxWavesPerBlock];
+    constexpr int U = 4;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const int wpb = (int)(blockDim.x / kWave);
+    const unsigned tile_shift = (unsigned)__builtin_ctz(blockDim.x / kWave) + (unsigned)__builtin_ctz(U);
+    const uint64_t ntiles = (pr.npieces + ((uint64_t)1 << tile_shift) - 1) >> tile_shift;
+    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_block;
+    const uint64_t t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
+    AllTiles at = {0u, aa.mode == kAllEmit, 0ull, aa.out, aa.capacity, s_wave};
+    if (aa.mode == kAllEmit) {
+        // only workgroups that hold one of the first `capacity` matches re-read their tiles
+        const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)aa.wg_count[blockIdx.x]);
+        const uint64_t rank = uniform64(aa.wg_rank[blockIdx.x]);
+        if (cnt == 0 || rank >= aa.capacity) return;
+        at.rank = rank;
+    }
+    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &at);
+    if (aa.mode == kAllEmit) return;
+    const uint32_t wc = wave_sum(at.lane_count);
+    if (lane == 0) s_wave[wave] = wc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < wpb; ++w) sum += s_wave[w];
+        if (aa.mode == kAllCountPerWorkgroup) aa.wg_count[blockIdx.x] = sum;
+        else if (sum != 0) __hip_atomic_fetch_add(aa.total, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

@@ -1,0 +1,226 @@
+// ss_matches.hip - every occurrence of a needle (include/sliceslice_hip_matches.h): ss_count_device / _async, ss_find_all_device.
+// NOT in libsliceslice_hip.so: libsliceslice_hip_matches.so holds the product's objects plus this file and scan_inst_all.hip.
+//
+// The scan is the find kernels' filter and verification with no early exit (scan_tiles<..., ALL = true>, scan_kernels.hpp):
+//   count        one launch; each workgroup adds its count to one 64-bit word (a device-scope atomic, only when it has matches).
+//   find_all     a count pass that writes one count per workgroup, the exclusive prefix sum of those counts (one workgroup), and an
+//                emit pass over the same grid in which only the workgroups that hold one of the first `capacity` matches re-read
+//                their tiles and write their offsets at their rank.  Workgroups take contiguous runs of tiles, so workgroup order is
+//                address order and the offsets land sorted.
+// The launch shape is the static one of an untuned search (ss_scan.hip, enqueue_scan with autotune off); the census is neither
+// started nor read, so a searcher's tuning state is the same before and after these calls, and the answers cannot depend on it.
+#include "ss_internal.hpp"
+
+#include "../../include/sliceslice_hip_matches.h"
+#include "matches_launch.hpp"
+
+namespace ssh {
+namespace {
+
+// ---- call-owned scratch ---------------------------------------------------------------------------------------------------
+// The workgroup counts, their prefix and the total of one call.  A call takes a buffer of its device from a free list (or
+// allocates one) and hands it back once its stream wait has returned, so two calls in flight - two threads, two streams - never
+// share one.  A call that fails keeps its buffer out of the list (work it enqueued may still be running).
+struct Scratch {
+    int dev = -1;
+    uint8_t *d = nullptr;
+    size_t bytes = 0;
+    uint64_t *h = nullptr;      // pinned: the total, read back
+};
+std::mutex g_scratch_mu;
+std::vector<Scratch> g_scratch_free;
+
+int take_scratch(int dev, size_t bytes, Scratch *out)
+{
+    {
+        std::lock_guard<std::mutex> lk(g_scratch_mu);
+        for (size_t k = 0; k < g_scratch_free.size(); ++k) {
+            if (g_scratch_free[k].dev == dev && g_scratch_free[k].bytes >= bytes) {
+                *out = g_scratch_free[k];
+                g_scratch_free.erase(g_scratch_free.begin() + (long)k);
+                return SS_OK;
+            }
+        }
+    }
+    Scratch sc;
+    sc.dev = dev;
+    sc.bytes = (bytes + 4095) & ~(size_t)4095;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc.d), sc.bytes));
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&sc.h), sizeof(uint64_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipFree(sc.d);
+        return fail(SS_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e));
+    }
+    *out = sc;
+    return SS_OK;
+}
+
+struct ScratchLease {
+    Scratch sc;
+    bool done = false;          // the call's stream wait has returned: nothing of it is still using the buffer
+    ~ScratchLease()
+    {
+        if (!done || !sc.d) return;
+        std::lock_guard<std::mutex> lk(g_scratch_mu);
+        g_scratch_free.push_back(sc);
+    }
+};
+
+// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (the rule of ss_scan.hip).
+uint32_t occupancy_pad(int occ, unsigned block)
+{
+    const uint32_t per = (160u * 1024u) / (uint32_t)occ;
+    const uint32_t fixed = (block / ss::kWave) * ss::kNeedleLds;
+    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
+    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
+    return pad;
+}
+
+// One all-matches launch of (searcher, haystack): the Problem (fill_problem, the searcher's own filter bytes) and the shape an
+// untuned search takes - workgroups per CU guessed from the needle, one or two contiguous tiles per workgroup.
+struct AllLaunch {
+    ss::Problem pr;
+    ss::Shape shape;
+    int q = 0, mode = 0;
+    bool one_byte = false;
+};
+
+int plan_all(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, AllLaunch *out)
+{
+    ProblemShape ps;
+    fill_problem(s, pd->d_needle, d_hay, len, 0, &out->pr, &ps, nullptr);
+    const bool one_byte = ps.one_byte;
+    const size_t fa = ps.fa, position = ps.position, position3 = ps.position3;
+    const bool text_like = !one_byte && ss::byte_rarity_rank(s->needle[fa]) >= 64 && ss::byte_rarity_rank(s->needle[fa + position]) >= 64 &&
+                           ss::byte_rarity_rank(s->needle[fa + position3]) >= 64;
+    const int occ = !one_byte && text_like && out->pr.d == 0 ? 6 : 4;
+    out->mode = out->pr.d == 0 ? 0 : 2;
+    out->one_byte = one_byte;
+    out->q = (int)((position % 16) / 4);
+    const unsigned block = ss::kBlock;
+    const uint64_t per_tile = (block / ss::kWave) * 4;                  // pieces per tile at U = 4
+    const uint64_t ntiles = (out->pr.npieces + per_tile - 1) / per_tile;
+    DeviceInfo di;
+    if (int rc = device_info(pd->dev, &di)) return rc;
+    uint64_t tpb = ntiles / ((uint64_t)di.cus * (out->mode == 0 ? 256 : 128));
+    if (tpb > 2) tpb = 2;
+    if (tpb < 1) tpb = 1;
+    uint64_t blocks = (ntiles + tpb - 1) / tpb;
+    while (blocks > 0x7fffffffull) {        // gridDim.x limit
+        tpb *= 2;
+        blocks = (ntiles + tpb - 1) / tpb;
+    }
+    if (blocks < 1) blocks = 1;
+    out->shape = {(unsigned)blocks, block, tpb, occupancy_pad(occ, block)};
+    return SS_OK;
+}
+
+int launch_all(const AllLaunch &al, hipStream_t st, const ss::AllArgs &aa)
+{
+    if (!ss::launch_scan_all(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa))
+        return fail(SS_ERR_ARGUMENT, "no all-matches kernel for mode %d, window %d", al.mode, al.q);
+    HIP_TRY(hipGetLastError());
+    return SS_OK;
+}
+
+int check_args(const ss_searcher *s, const void *d_haystack, size_t len, const void *out)
+{
+    if (!s || !out) return fail(SS_ERR_ARGUMENT, "NULL argument");
+    if (len && !d_haystack) return fail(SS_ERR_ARGUMENT, "haystack is NULL");
+    return SS_OK;
+}
+
+}  // namespace
+}  // namespace ssh
+
+using namespace ssh;
+
+extern "C" {
+
+int ss_count_device_async(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_count)
+{
+    if (int rc = check_args(s, d_haystack, len, d_count)) return rc;
+    SearchGate gate(s);                                  // set_filter* are refused while this call runs
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PerDevice *pd = nullptr;
+    if (int rc = get_per_device(s, &pd)) return rc;
+    s->used_async.store(true, std::memory_order_release);
+    if (s->n == 0) {                                     // len + 1 empty matches
+        HIP_TRY(ss::launch_store_u64(d_count, (uint64_t)len + 1, st));
+        return SS_OK;
+    }
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
+    if (len < s->n) return SS_OK;
+    AllLaunch al;
+    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    const ss::AllArgs aa = {d_count, nullptr, nullptr, nullptr, 0, ss::kAllCount};
+    return launch_all(al, st, aa);
+}
+
+int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
+{
+    if (int rc = check_args(s, d_haystack, len, count)) return rc;
+    SearchGate gate(s);
+    if (s->n == 0) { *count = (uint64_t)len + 1; return SS_OK; }
+    if (len < s->n) { *count = 0; return SS_OK; }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    PerDevice *pd = nullptr;
+    if (int rc = get_per_device(s, &pd)) return rc;
+    AllLaunch al;
+    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    ScratchLease lease;
+    if (int rc = take_scratch(pd->dev, sizeof(uint64_t), &lease.sc)) return rc;
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
+    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));
+    const ss::AllArgs aa = {d_total, nullptr, nullptr, nullptr, 0, ss::kAllCount};
+    if (int rc = launch_all(al, st, aa)) return rc;
+    HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    lease.done = true;
+    *count = *lease.sc.h;
+    return SS_OK;
+}
+
+int ss_find_all_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_offsets,
+                       uint64_t capacity, uint64_t *count)
+{
+    if (int rc = check_args(s, d_haystack, len, count)) return rc;
+    if (capacity && !d_offsets) return fail(SS_ERR_ARGUMENT, "offsets are NULL with a capacity of %llu", (unsigned long long)capacity);
+    SearchGate gate(s);
+    if (len < s->n) { *count = 0; return SS_OK; }
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (s->n == 0) {                                     // offsets 0 .. len
+        const uint64_t total = (uint64_t)len + 1;
+        if (capacity) {
+            HIP_TRY(ss::launch_iota(d_offsets, total < capacity ? total : capacity, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        *count = total;
+        return SS_OK;
+    }
+    PerDevice *pd = nullptr;
+    if (int rc = get_per_device(s, &pd)) return rc;
+    AllLaunch al;
+    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    const uint64_t blocks = al.shape.blocks;
+    // [total u64][rank u64 x blocks][count u32 x blocks]
+    ScratchLease lease;
+    if (int rc = take_scratch(pd->dev, 8 + blocks * 12, &lease.sc)) return rc;
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
+    uint64_t *d_rank = d_total + 1;
+    uint32_t *d_wg = reinterpret_cast<uint32_t *>(d_rank + blocks);
+    const ss::AllArgs counting = {nullptr, d_wg, nullptr, nullptr, 0, ss::kAllCountPerWorkgroup};
+    if (int rc = launch_all(al, st, counting)) return rc;
+    HIP_TRY(ss::launch_prefix(d_wg, blocks, d_rank, d_total, st));
+    if (capacity) {
+        const ss::AllArgs emitting = {nullptr, d_wg, d_rank, d_offsets, capacity, ss::kAllEmit};
+        if (int rc = launch_all(al, st, emitting)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    lease.done = true;
+    *count = *lease.sc.h;
+    return SS_OK;
+}
+
+}  // extern "C"

@@ -96,6 +96,13 @@ SERVICE_ABI = {
     "ss_service_bind": (_int, [_vp, _vp, _sz]),
     "ss_service_stop": (None, [_vp]),
 }
+# include/sliceslice_hip_matches.h: every occurrence (count, find-all) - NOT in the product library: libsliceslice_hip_matches.so
+# (the product's objects plus the all-matches scan) holds it
+MATCHES_ABI = {
+    "ss_count_device": (_int, [_vp, _vp, _sz, _vp, _pu64]),
+    "ss_count_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -192,9 +199,11 @@ def _load(path):
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
     _bind(L, ABI, strict=True)
     _bind(L, SERVICE_ABI, strict=False)
+    _bind(L, MATCHES_ABI, strict=False)
     _bind(L, HOOKS_ABI, strict=False)
     L.has_hooks = hasattr(L, "ss_debug_fail_next_scans")
     L.has_service = hasattr(L, "ss_service_start")
+    L.has_matches = hasattr(L, "ss_count_device")
     return L
 
 
@@ -210,6 +219,7 @@ def lib():
 _tools = None
 _tuning = None
 _service = None
+_matches = None
 
 
 def tools_lib():
@@ -256,6 +266,32 @@ class service_build:
         global _lib
         _lib = self._saved
         return False
+
+
+class matches_build:
+    """``with ss.matches_build():`` - inside the block ``lib()`` is libsliceslice_hip_matches.so: every function of the product
+    library plus the all-matches scan (include/sliceslice_hip_matches.h: ``count`` / ``find_all``).  Searchers belong to the library
+    that made them, so the searchers whose ``count`` / ``find_all`` are called must be created inside the block; they keep working
+    after it."""
+
+    def __enter__(self):
+        global _lib, _matches
+        if _matches is None:
+            _matches = _load(_build.build_matches())
+        self._saved, _lib = _lib, _matches
+        return _matches
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = self._saved
+        return False
+
+
+def _matches_lib(L):
+    if not getattr(L, "has_matches", False):
+        raise SlicesliceError(SS_ERR_ARGUMENT, "count / find_all are not part of libsliceslice_hip.so: they live in "
+                                               "libsliceslice_hip_matches.so - create the searcher inside `with ss.matches_build():`")
+    return L
 
 
 def _hooks(L):
@@ -414,6 +450,67 @@ class DynamicHipSearcher:
             st = stream if stream is not None else _current_stream_handle()
             self._ck(self._L.ss_search_device_async(self._h, haystack.data_ptr(), haystack.numel(), st, d_flag.data_ptr()))
 
+    # -- every occurrence (libsliceslice_hip_matches.so: searchers made inside `with ss.matches_build():`) ----------------
+    @staticmethod
+    def _device_haystack(haystack):
+        """(pointer, length, device tensor) of a haystack: device tensors as they are, host bytes uploaded to the current device."""
+        if isinstance(haystack, tuple):
+            return haystack[0], haystack[1], None
+        import torch
+        if not _is_tensor(haystack):
+            haystack = torch.from_numpy(np.frombuffer(bytes(haystack), dtype=np.uint8).copy())
+        if not haystack.is_cuda:
+            haystack = haystack.contiguous().view(torch.uint8).cuda()
+        if haystack.dtype.itemsize != 1 or not haystack.is_contiguous():
+            raise TypeError("device haystack must be a contiguous 1-byte tensor")
+        return haystack.data_ptr(), haystack.numel(), haystack
+
+    def count(self, haystack, stream=None):
+        """int: the number of (overlapping) occurrences of the needle in ``haystack`` (ss_count_device).  Empty needle: len + 1."""
+        L = _matches_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_count_device(self._h, ptr, length, st, ctypes.byref(c)))
+        return c.value
+
+    def count_async(self, haystack, d_count, stream=None):
+        """Enqueue only (ss_count_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
+        L = _matches_lib(self._L)
+        with _on_device_of(haystack):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_count_device_async(self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
+
+    def find_all(self, haystack, capacity=None, stream=None):
+        """int64 tensor on the haystack's device: the offsets of every (overlapping) occurrence in ascending order
+        (ss_find_all_device).  capacity=None: counted first, then exactly that many; else the leftmost ``capacity`` of them."""
+        import torch
+        L = _matches_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            if capacity is None:
+                self._ck(L.ss_count_device(self._h, ptr, length, st, ctypes.byref(total)))
+                capacity = total.value
+            out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+            self._ck(L.ss_find_all_device(self._h, ptr, length, st, out.data_ptr() if capacity else None, int(capacity),
+                                          ctypes.byref(total)))
+        return out[:min(int(capacity), total.value)]
+
+    def find_all_into(self, haystack, d_offsets, stream=None):
+        """ss_find_all_device into a caller's 8-byte device tensor (capacity = its length); returns the total count."""
+        L = _matches_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_find_all_device(self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None,
+                                          d_offsets.numel(), ctypes.byref(total)))
+        return total.value
+
     # -- tuning / measurement hooks ------------------------------------------------------------------
     @property
     def filter(self):
@@ -532,6 +629,12 @@ class MemchrHipSearcher:
 
     def find(self, haystack, stream=None):
         return self._inner.find(haystack, stream)
+
+    def count(self, haystack, stream=None):
+        return self._inner.count(haystack, stream)
+
+    def find_all(self, haystack, capacity=None, stream=None):
+        return self._inner.find_all(haystack, capacity, stream)
 
 
 def shard_range(length, needle_len, nranks, rank):

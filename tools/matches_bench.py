@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""./matches_bench.py [--gib 1,8] [--reps 20] - rates of every-occurrence search (libsliceslice_hip_matches.so), a measurement aid
+(nothing here is asserted).  One JSON line per case:
+  absent     random bytes, a 16-byte needle that does not occur: count and search_in ALTERNATING in one process on one buffer with
+             autotune off (the same filter over the same loads), and find_all (count pass + prefix + an emit grid that leaves at once)
+  density    planted needles at 1 per MiB and 1 per KiB (1 GiB of random bytes): count and find_all
+  text       common words of tests/golden/data/i386.txt, the text tiled to 1 GiB: count and find_all (candidate-dense, no early exit)
+Times are hipEvent pairs around the synchronous call (launches included), median of --reps."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sliceslice_rs_amd as ss  # noqa: E402
+
+
+def timed(fn, reps):
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def emit(row):
+    print(json.dumps(row), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", default="1,8")
+    ap.add_argument("--reps", type=int, default=20)
+    args = ap.parse_args()
+    needle = bytes(range(0x61, 0x71))
+    with ss.matches_build():
+        ss.set_autotune(False)                          # (the matches library's own switch: it is a library of its own)
+        s = ss.DynamicHipSearcher.new(needle)
+    for gib in [float(g) for g in args.gib.split(",")]:
+        n_bytes = int(gib * (1 << 30))
+        hay = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+        ss.fill_random_device(hay, 0x5EED0777)
+        assert s.count(hay) == 0
+        c_ms, s_ms = [], []
+        for _ in range(args.reps):                      # alternating
+            c_ms.append(timed(lambda: s.count(hay), 1))
+            s_ms.append(timed(lambda: s.search_in(hay), 1))
+        f_ms = timed(lambda: s.find_all(hay, capacity=1024), args.reps)
+        c, se = statistics.median(c_ms), statistics.median(s_ms)
+        emit({"case": "absent", "gib": gib, "count_ms": c, "search_in_ms": se, "count_over_search_rate": se / c, "find_all_ms": f_ms,
+              "find_all_minus_count_us": (f_ms - c) * 1e3, "count_gbps": n_bytes / c / 1e6})
+        del hay
+        torch.cuda.empty_cache()
+    n_bytes = 1 << 30
+    hay = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+    nt = torch.tensor(list(needle), dtype=torch.uint8, device="cuda")
+    for per, label in ((1 << 20, "1/MiB"), (1 << 10, "1/KiB")):
+        ss.fill_random_device(hay, 0x5EED0778)
+        hay.view(-1, per)[:, 100:116] = nt
+        total = s.count(hay)
+        c = timed(lambda: s.count(hay), args.reps)
+        f = timed(lambda: s.find_all(hay, capacity=total), args.reps)
+        emit({"case": "density", "per": label, "matches": total, "count_ms": c, "find_all_ms": f, "count_gbps": n_bytes / c / 1e6,
+              "find_all_gbps": n_bytes / f / 1e6})
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "data", "i386.txt"), "rb").read()
+    reps_t = n_bytes // len(text) + 1
+    hay = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda().repeat(reps_t)[:n_bytes].contiguous()
+    for w in (b"the", b"instruction", b"register", b"Intel"):
+        with ss.matches_build():
+            sw = ss.DynamicHipSearcher.new(w)
+        total = sw.count(hay)
+        c = timed(lambda: sw.count(hay), args.reps)
+        f = timed(lambda: sw.find_all(hay, capacity=total), args.reps)
+        emit({"case": "text", "word": w.decode(), "matches": total, "count_ms": c, "find_all_ms": f, "count_gbps": n_bytes / c / 1e6,
+              "find_all_gbps": n_bytes / f / 1e6})
+
+
+if __name__ == "__main__":
+    main()
