@@ -561,7 +561,8 @@ __global__ void __launch_bounds__(kBlock) batch_cold_kernel(const BatchArgs a, c
 // workgroups that leave early because the needle has been found still had to count (the reference's 4,585-needle loop: 0.190 ms
 // instead of 0.178).  So:
 //   * a problem scanned by ONE workgroup (eff == 1): a match goes to a word in the workgroup's LDS (scan_tiles' wg_sink) and the
-//     workgroup publishes the answer with one store - no state word, no atomic, no second kernel;
+//     workgroup publishes the answer with one store - no state word is read, no atomic, no second kernel (a plan's run that has
+//     state words stores them idle behind the answer: see PlanCtl);
 //   * a problem scanned by several: they work on the plan's own state word (flag / minimum, the others stop early) exactly as the
 //     unplanned kernel works on the caller's output, and batch_publish_kernel - one lane per problem, launched behind the scan
 //     only by plans that have such problems - copies the state word to the output and puts it back to idle.
@@ -588,6 +589,12 @@ __global__ void __launch_bounds__(kBlock) batch_cold_kernel(const BatchArgs a, c
 //     re-read, or it came later - then so did its output store, behind the idle value.  FIND: the same with minima.
 //   * the tally of found problems (plans with two layouts): the first finder of a problem adds one to tally[parity]; workgroup 0 of
 //     the NEXT run stores the previous run's count to pinned memory and clears it.
+//   * INVARIANT: a problem scanned by one workgroup never reads a state word and leaves both idle.  Its waves poll the always-idle
+//     word of its cold record and match into LDS; thread 0 stores the idle value into both halves when it publishes.  A plan of
+//     long problems holds two layouts whose slice counts differ (round robin: eff = ceil(tiles / 4); contiguous runs: ceil(tiles /
+//     8)), so a problem of 5 to 8 tiles has an opener in one layout and none in the other: without the invariant a word raised by a
+//     round-robin run stayed raised through the contiguous runs (every second one stopped at its first poll and published 0, or cut
+//     a find short) and came back as a stale answer after the switch back to round robin (tests/test_gpu_widen.py).
 struct __attribute__((aligned(64))) PlanCtl {
     unsigned long long run_word;                    // (identity of the latest run) << 1 | its parity
     uint32_t tally[2];                              // by parity: problems found (scanned by several workgroups) in that run
@@ -693,14 +700,16 @@ scan_batched_plan_kernel(const BatchArgs a, const BatchDesc *__restrict__ descs,
             __hip_atomic_store(&ctl->run_word, (me << 1) | parity, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    // (MULTI = false: every problem publishes from LDS; the word the tiles poll is the idle one in the cold record, as in the calls)
+    const uint32_t eff = (uint32_t)(d.per >> 32), per = (uint32_t)d.per;
+    // A problem scanned by one workgroup (MULTI = false: every problem) publishes from LDS; the word its tiles poll is the idle one in
+    // the cold record, as in the calls - never a PlanState word, which the other layout of the plan may have left raised (see PlanCtl)
+    const bool shared = MULTI && eff > 1;
     const int seen = MULTI ? (parity ? seen1 : seen0) : seen0;
-    int *found = FIND ? nullptr : (MULTI ? reinterpret_cast<int *>(&states[prob].half[parity].word) : reinterpret_cast<int *>(&rec->pad[1]));
-    void *sink = FIND ? (MULTI ? static_cast<void *>(&states[prob].half[parity].word) : static_cast<void *>(&rec->pad[0])) : static_cast<void *>(found);
+    int *found = FIND ? nullptr : (shared ? reinterpret_cast<int *>(&states[prob].half[parity].word) : reinterpret_cast<int *>(&rec->pad[1]));
+    void *sink = FIND ? (shared ? static_cast<void *>(&states[prob].half[parity].word) : static_cast<void *>(&rec->pad[0])) : static_cast<void *>(found);
     const uint32_t mis = d.shifts & 15;
     const uint64_t npieces = ((mis + d.end + 15) / 16 + 63) / 64;
     const uint64_t ntiles = (npieces + kWavesPerBlock * U - 1) / (kWavesPerBlock * U);
-    const uint32_t eff = (uint32_t)(d.per >> 32), per = (uint32_t)d.per;
     if (slice >= eff) {                             // surplus slice, or a problem that needs no scan (eff == 0)
         if (COUNTED && eff == 0 && slice == 0 && threadIdx.x == 0) {
             if (FIND) a.best[prob] = d.n == 0 ? 0ull : ~0ull;
@@ -799,6 +808,12 @@ scan_batched_plan_kernel(const BatchArgs a, const BatchDesc *__restrict__ descs,
             }
             if (FIND) a.best[prob] = mine;
             else a.found[prob] = mine != 0;
+            if (MULTI) {
+                // both of the problem's state words idle: a later run in a layout that scans it with several workgroups starts from
+                // idle whatever its parity (nobody else touches them in this run - runs of a plan are ordered on their stream)
+                __hip_atomic_store(&states[prob].half[0].word, FIND ? ~0ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&states[prob].half[1].word, FIND ? ~0ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
 }

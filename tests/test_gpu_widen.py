@@ -469,7 +469,9 @@ def test_plans_of_long_problems_change_their_layout_with_what_the_last_run_found
     """A plan of LONG problems holds two layouts: round robin (side by side through each haystack: the fastest full scan) and eight
     contiguous runs per problem (later runs of a found problem leave at once).  A run tallies the problems it found; a later run
     takes the contiguous runs when at least an eighth were found.  Answers are the same through every switch, for flags
-    and offsets, with the needles present, removed and put back."""
+    and offsets, with the needles present, removed and put back.  Every problem here is scanned by several workgroups in both
+    layouts; problems whose count of workgroups differs between the layouts - a problem scanned by one workgroup never reads a
+    state word and leaves both idle - are the layout-switch tests below."""
     count, each = 160, 2 << 20
     hay = torch.empty(count * each, dtype=torch.uint8, device="cuda")
     ss.fill_random_device(hay, 0xA17)
@@ -526,3 +528,305 @@ def test_plans_of_long_problems_change_their_layout_with_what_the_last_run_found
         few = ss.BatchPlan(hay, (torch.arange(5, dtype=torch.int64) * (40 * each)).cuda(), needles[:64], noff[:5])
         assert not few.layout()["two"]
         few.close()
+
+
+# ---- plan runs across layout switches: problems whose count of workgroups differs between the two layouts -----------------------
+# (restated from ss_batched.hip / batched_kernels.hpp, so that a change of constants that empties the window below fails here)
+_TILE = 16 << 10                    # a tile: 4 waves x 4 pieces x 64 lanes x 16 bytes
+_MIN_TILES_MAIN = 4                 # kPlanMinTilesLong: the main (round-robin) layout of a plan of long problems
+_MIN_TILES_SECOND = 8               # kPlanMinTilesCounted: the second layout (contiguous runs)
+_SECOND_SLICES = 8                  # kPlanSliceMajorMax: the second layout's slices per problem at most
+
+
+def _plan_tiles(addr, length, n, anchor):
+    """Tiles a plan scans for a problem (batched_kernels.hpp, plan_one): the window starts at the first filter byte, aligned down."""
+    mis = (addr + anchor) & 15
+    return -(-(mis + length - n + 1) // _TILE)
+
+
+def _plan_eff(tiles, min_tiles, slices):
+    return max(1, min(-(-tiles // min_tiles), slices))
+
+
+class _SwitchBatch:
+    """(needle, haystack) problems for plans that switch layouts, kept on the device and mirrored on the host.  Haystack bytes are
+    random below 0x80; every needle holds one byte of 0x80 or above, so it occurs only where it has been planted.  Every edit goes
+    to both copies; expected answers are bytes.find on the host copy (recomputed for the problems an edit touched)."""
+
+    def __init__(self, ss, rng, kinds):
+        # kinds: list of (haystack length, needle length, misalignment of the haystack's first byte)
+        self.count = len(kinds)
+        self.begin, self.end, cur = [], [], 0
+        for length, _, mis in kinds:
+            cur = (cur + 15) & ~15
+            self.begin.append(cur + mis)
+            self.end.append(cur + mis + length)
+            cur += mis + length
+        total = cur + 256
+        self.bg = (ss.fill_random_host(total, rng.randrange(1 << 30)) & 0x7F).astype(np.uint8)
+        self.host = self.bg.copy()
+        self.hay = torch.from_numpy(self.host).cuda()
+        self.needles = []
+        for _, n, _ in kinds:
+            nd = bytearray(rng.randrange(0x80) for _ in range(n))
+            nd[rng.randrange(n)] = 0x80 + rng.randrange(0x80)
+            self.needles.append(bytes(nd))
+        noff = np.zeros(self.count + 1, dtype=np.int64)
+        noff[1:] = np.cumsum([len(nd) for nd in self.needles])
+        self.nbuf = torch.from_numpy(np.frombuffer(b"".join(self.needles), dtype=np.uint8).copy()).cuda()
+        self.noff = torch.from_numpy(noff).cuda()
+        self.ranges = (torch.tensor(self.begin, dtype=torch.int64, device="cuda"), torch.tensor(self.end, dtype=torch.int64, device="cuda"))
+        self.planted = [None] * self.count
+        self._want = [None] * self.count
+
+    def length(self, p):
+        return self.end[p] - self.begin[p]
+
+    def spot(self, p, where):
+        """An offset in problem p's haystack: "start", "middle", "last" (the last possible offset)."""
+        last = self.length(p) - len(self.needles[p])
+        return {"start": 0, "middle": last // 2, "last": last}[where]
+
+    def _write(self, a, b):
+        self.hay[a:b] = torch.from_numpy(self.host[a:b].copy()).cuda()
+        for p in range(self.count):
+            if self.begin[p] < b and a < self.end[p]:
+                self._want[p] = None
+
+    def plant(self, p, at):
+        assert self.planted[p] is None, p
+        a = self.begin[p] + at
+        self.host[a:a + len(self.needles[p])] = np.frombuffer(self.needles[p], dtype=np.uint8)
+        self._write(a, a + len(self.needles[p]))
+        self.planted[p] = at
+
+    def remove(self, p):
+        at, self.planted[p] = self.planted[p], None
+        if at is not None:
+            a = self.begin[p] + at
+            self.host[a:a + len(self.needles[p])] = self.bg[a:a + len(self.needles[p])]
+            self._write(a, a + len(self.needles[p]))
+
+    def reset(self):
+        self.host[:] = self.bg
+        self.hay.copy_(torch.from_numpy(self.bg))
+        self.planted = [None] * self.count
+        self._want = [None] * self.count
+
+    def want(self, find):
+        for p in range(self.count):
+            if self._want[p] is None:
+                self._want[p] = self.host[self.begin[p]:self.end[p]].tobytes().find(self.needles[p])
+        return list(self._want) if find else [1 if w >= 0 else 0 for w in self._want]
+
+    def plan(self, ss, find):
+        return ss.BatchPlan(self.hay, None, self.nbuf, self.noff, find=find, hay_ranges=self.ranges)
+
+
+class _PlanRunner:
+    """Runs a plan, checks every run problem by problem against the host bytes, and records the layout each run took."""
+
+    def __init__(self, batch, plan, find, hooks, tag, info=None):
+        self.batch, self.plan, self.find, self.hooks, self.tag = batch, plan, find, hooks, tag
+        self.info = info or (lambda p: "")
+        self.layouts = []
+
+    def next_is_second(self):
+        return self.plan.layout()["next_is_second"] if self.hooks else None
+
+    def run(self):
+        second = self.next_is_second()
+        got = self.plan.run().tolist()
+        torch.cuda.synchronize()
+        want = self.batch.want(self.find)
+        bad = [(p, self.info(p), want[p], got[p]) for p in range(self.batch.count) if got[p] != want[p]]
+        assert not bad, (f"{self.tag} find={self.find} run {len(self.layouts)} (second layout: {second}): {len(bad)} wrong, "
+                         f"(problem, kind, want, got): {bad[:12]}")
+        self.layouts.append(second)
+        return second
+
+
+def _switch_kinds(rng, n_long=140):
+    """~192 problems: n_long of 2 MiB (they make the plan long and carry the tally), and short ones of 3 to 10 tiles at and around
+    tile boundaries - lengths k * 16 KiB + {-1, 0, 1}, and the same boundaries of the scanned window itself."""
+    kinds = []
+    for k in range(3, 11):
+        for d in (-1, 0, 1):
+            n = rng.choice((1, 4, 16, 40))
+            kinds.append((k * _TILE + d, n, rng.randrange(16)))
+            n, mis = rng.choice((1, 4, 16)), rng.randrange(16)
+            kinds.append((k * _TILE + d + n - 1 - mis, n, mis))        # (needles of <= 16 bytes: the scan starts at needle[0])
+    kinds += [(5 * _TILE, 40, 3), (8 * _TILE, 40, 15), (5 * _TILE + 1, 1, 0), (8 * _TILE - 1, 16, 7)]
+    kinds += [(2 << 20, rng.choice((1, 4, 16, 40)), rng.randrange(16)) for _ in range(n_long)]
+    order = list(range(len(kinds)))
+    rng.shuffle(order)                                                  # long and short problems interleaved
+    return [kinds[i] for i in order]
+
+
+@pytest.fixture(scope="module")
+def switch_batch(ss):
+    return _SwitchBatch(ss, random.Random(0x5A17), _switch_kinds(random.Random(0x5A17)))
+
+
+def _switch_sequence(ss, batch, find, hooks, tag):
+    """Needles present -> the second layout; needles moved right and removed while in it; the long problems' needles and half of the
+    short ones removed -> round robin again; everything put back -> the second layout again.  Returns the layouts the runs took."""
+    B = batch
+    B.reset()
+    rng = random.Random(7 + find)
+    is_long = [B.length(p) >= (1 << 20) for p in range(B.count)]
+    shorts = [p for p in range(B.count) if not is_long[p]]
+    where = ("start", "middle", "last")
+    home = {p: B.spot(p, where[p % 3]) for p in range(B.count)}
+    for p in range(B.count):
+        B.plant(p, home[p])
+    plan = B.plan(ss, find)
+    info = lambda p: "long" if is_long[p] else f"{B.length(p)} B / needle {len(B.needles[p])}"   # noqa: E731
+    if hooks:
+        lay = plan.layout()
+        main_slices, second_slices = lay["slices"]
+        assert lay["two"] and main_slices > _SECOND_SLICES and 1 < second_slices <= _SECOND_SLICES and not lay["next_is_second"], lay
+        window = []
+        for p in shorts:
+            tri, _, eff = plan.filter_of(p)
+            tiles = _plan_tiles(B.hay.data_ptr() + B.begin[p], B.length(p), len(B.needles[p]), tri[0])
+            assert 3 <= tiles <= 11 and eff == _plan_eff(tiles, _MIN_TILES_MAIN, main_slices), (p, info(p), tri, tiles, eff)
+            e2 = _plan_eff(tiles, _MIN_TILES_SECOND, second_slices)
+            if (eff, e2) == (2, 1):
+                window.append(p)
+            if tiles in (5, 8):
+                assert eff == 2, (p, tiles, eff)
+        # problems scanned by two workgroups in the main layout and by one in the second: the case this sequence is about
+        assert len(window) >= 16, len(window)
+        info = lambda p: "long" if is_long[p] else f"{B.length(p)} B / needle {len(B.needles[p])} / eff {plan.filter_of(p)[2]}"  # noqa: E731
+    R = _PlanRunner(B, plan, find, hooks, tag, info)
+    try:
+        # 1. every needle present: two round-robin runs, then the second layout from the tally on
+        for _ in range(8):
+            R.run()
+        # 2. in the second layout the short problems' needles move right (removed at X, planted at Y > X), some leave altogether
+        if hooks:
+            assert R.next_is_second()
+        for i, p in enumerate(shorts):
+            B.remove(p)
+            if i % 5 == 4:
+                continue
+            at = home[p]
+            later = B.spot(p, "last") if at < B.spot(p, "last") else None
+            if later is None or at == later:
+                later = B.spot(p, "middle") if at == 0 else None
+            if later is not None and i % 2:
+                later = rng.randrange(at + 1, later + 1)
+            B.plant(p, later if later is not None else at)
+        for _ in range(4):
+            R.run()
+        # 3. back to round robin: the long problems' needles leave, and half of the short ones'.  The host hears of a run's tally
+        # from the run after it, so two more runs take the second layout.  The words a switch back can find raised are those of the
+        # last round-robin run (run 1): the first round-robin run is made one of run 1's parity (an odd run)
+        if len(R.layouts) % 2 == 0:
+            R.run()
+        for p in range(B.count):
+            if is_long[p] or shorts.index(p) % 2:
+                B.remove(p)
+        R.run()
+        R.run()
+        if hooks:
+            assert R.layouts[-2:] == [True, True] and not R.next_is_second(), R.layouts
+        back = len(R.layouts)
+        assert back % 2 == 1
+        R.run()
+        R.run()                                                         # one round-robin run of each parity
+        if hooks:
+            assert R.layouts[back:] == [False, False] and not R.next_is_second(), R.layouts
+        # 4. everything back where it was: two more round-robin runs (the tally's delay), then the second layout again
+        for p in range(B.count):
+            B.remove(p)
+            B.plant(p, home[p])
+        for _ in range(5):
+            R.run()
+        if hooks:
+            assert R.layouts[-5:] == [False, False, True, True, True], R.layouts
+    finally:
+        plan.close()
+    return R.layouts
+
+
+def test_plan_layout_switches_leave_no_stale_state_across_mixed_problem_sizes(ss, switch_batch):
+    """A plan of long and short problems: a short problem of 5 to 8 tiles is scanned by two workgroups in the main layout and by
+    ONE in the second.  A problem scanned by one workgroup reads no state word and leaves both of its words idle, so no layout
+    change hands a run a word raised by an older run - neither a false negative (runs in the second layout, needles unchanged or
+    moved right) nor a false positive or an old offset (runs after the switch back, needles removed)."""
+    with ss.tuning_build():
+        for find in (False, True):
+            lay = _switch_sequence(ss, switch_batch, find, True, "mixed")
+            assert lay[:2] == [False, False] and all(lay[2:8]), lay     # runs 0, 1 round robin; the second layout from then on
+            assert sum(lay) >= 12 and lay.count(False) >= 5, lay
+
+
+def test_plan_layout_switch_sequence_with_one_layout_gives_the_same_answers(ss, switch_batch):
+    """The control: the same sequence on plans held to one layout (SLICESLICE_PLAN_ONE_LAYOUT, hooks builds) - the expected
+    answers and the planting are right independently of the layout switch."""
+    with ss.tuning_build():
+        for find in (False, True):
+            os.environ["SLICESLICE_PLAN_ONE_LAYOUT"] = "1"
+            try:
+                plan = switch_batch.plan(ss, find)
+            finally:
+                del os.environ["SLICESLICE_PLAN_ONE_LAYOUT"]
+            assert not plan.layout()["two"]
+            plan.close()
+            os.environ["SLICESLICE_PLAN_ONE_LAYOUT"] = "1"
+            try:
+                # (the sequence makes its plans itself: the variable holds for all of them)
+                layouts = _switch_sequence(ss, switch_batch, find, False, "one layout")
+            finally:
+                del os.environ["SLICESLICE_PLAN_ONE_LAYOUT"]
+            assert len(layouts) >= 20
+
+
+def test_plan_layout_switch_sequence_on_the_product_library(ss, switch_batch):
+    """The library that ships (no test hooks: answers only) through the same layout switches."""
+    for find in (False, True):
+        assert len(_switch_sequence(ss, switch_batch, find, False, "product")) >= 20
+
+
+def test_plan_layout_switch_campaign(ss):
+    """Seeded random mixes of tile-boundary lengths and long haystacks; between runs needles are planted, moved and removed at
+    random.  Every run of every plan is checked problem by problem."""
+    seconds = switches = 0
+    with ss.tuning_build():
+        for seed in range(4):
+            rng = random.Random(0xC0FFEE + seed)
+            kinds = [(rng.randrange(3, 11) * _TILE + rng.choice((-1, 0, 1)), rng.choice((1, 4, 16, 40)), rng.randrange(16))
+                     for _ in range(rng.randrange(96, 124))]
+            kinds += [(rng.choice((2 << 20, (3 << 20) // 2)), rng.choice((4, 16, 40)), rng.randrange(16)) for _ in range(rng.randrange(28, 40))]
+            rng.shuffle(kinds)
+            B = _SwitchBatch(ss, rng, kinds)
+            for p in range(B.count):
+                if rng.random() < 0.8:
+                    B.plant(p, B.spot(p, rng.choice(("start", "middle", "last"))))
+            find = seed % 2 == 1
+            plan = B.plan(ss, find)
+            assert plan.layout()["two"], (seed, plan.layout())
+            R = _PlanRunner(B, plan, find, True, f"campaign seed {seed}")
+            try:
+                for run in range(12):
+                    R.run()
+                    drop = rng.choice((0.05, 0.2, 0.6)) if run >= 3 else 0.05
+                    for p in range(B.count):
+                        r = rng.random()
+                        if r < drop:
+                            B.remove(p)
+                        elif r < drop + 0.15:
+                            old = B.planted[p]
+                            B.remove(p)
+                            last = B.spot(p, "last")
+                            B.plant(p, rng.randrange(old, last + 1) if old is not None else rng.randrange(last + 1))
+                        elif B.planted[p] is None and r > 0.7:
+                            B.plant(p, rng.choice((0, B.spot(p, "middle"), B.spot(p, "last"), rng.randrange(B.spot(p, "last") + 1))))
+            finally:
+                plan.close()
+            seconds += sum(R.layouts)
+            switches += sum(a != b for a, b in zip(R.layouts, R.layouts[1:]))
+            del B
+    assert seconds >= 8 and switches >= 3, (seconds, switches)
