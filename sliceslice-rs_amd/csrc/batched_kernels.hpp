@@ -3,6 +3,14 @@
 #pragma once
 #include "scan_kernels.hpp"
 
+// The non-template kernels of this header have external linkage: ss_batched.hip is their home.  Another translation unit of a
+// library that holds ss_batched.hip too (batched_all_kernels.hpp) defines this as internal linkage before including the header,
+// and - kernels are emitted into the device code whether launched or not - SS_BATCH_COLD_KERNEL_ONLY, which leaves it
+// batch_cold_kernel (and the device functions and types) alone.
+#ifndef SS_BATCH_KERNEL_LINKAGE
+#define SS_BATCH_KERNEL_LINKAGE
+#endif
+
 namespace ss {
 
 // ---- K4: batched, one grid for many (needle, haystack) problems ----------------------------------
@@ -110,7 +118,8 @@ struct BatchClasses {
 };
 // `h_tag` (may be null): a pinned word that takes `tag` when the classes are in place - how the unplanned calls, which never wait,
 // learn that a sampling launched in front of an earlier call has finished (ss_batched.hip).
-__global__ void __launch_bounds__(kBlock) batch_sample_kernel(const uint8_t *haystacks, const uint64_t *hay_begin, const uint64_t *hay_end,
+#ifndef SS_BATCH_COLD_KERNEL_ONLY
+SS_BATCH_KERNEL_LINKAGE __global__ void __launch_bounds__(kBlock) batch_sample_kernel(const uint8_t *haystacks, const uint64_t *hay_begin, const uint64_t *hay_end,
                                                                uint64_t count, BatchClasses *out, unsigned long long *h_tag,
                                                                unsigned long long tag)
 {
@@ -177,6 +186,7 @@ __global__ void __launch_bounds__(kBlock) batch_sample_kernel(const uint8_t *hay
         if (h_tag) __hip_atomic_store(h_tag, tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+#endif
 constexpr uint32_t kClassNone = 255;            // above every class of either table
 
 // What the plan kernel tells the host about a plan's problems (ss_batch_plan_create sizes the grid of the runs from it).
@@ -312,7 +322,8 @@ __device__ __forceinline__ uint32_t plan_one(const BatchArgs &a, uint64_t prob, 
 // (out-of-range slots re-read byte 0 of the window) that are all in flight together; a first cut with a predicated
 // load-rank loop ran 8-12 us, one memory round trip per byte.
 // `stats` (plans only, else null): see PlanStats.
-__global__ void __launch_bounds__(kBlock) batch_plan_kernel(const BatchArgs a, uint64_t count, BatchDesc *descs,
+#ifndef SS_BATCH_COLD_KERNEL_ONLY
+SS_BATCH_KERNEL_LINKAGE __global__ void __launch_bounds__(kBlock) batch_plan_kernel(const BatchArgs a, uint64_t count, BatchDesc *descs,
                                                              uint32_t nslices, uint32_t min_tiles, int tile_pieces, PlanStats *stats,
                                                              const uint8_t *cls, BatchCold *colds)
 {
@@ -363,6 +374,7 @@ __global__ void __launch_bounds__(kBlock) batch_plan_kernel(const BatchArgs a, u
     }
     if (live) (void)plan_one(a, pi, h0, h1, n0, n1, given, descs, nslices, min_tiles, tile_pieces, s_class, &tiles, free_pair, colds);
 }
+#endif
 
 // The cold fields of a planned problem, re-read from its descriptor by the waves that need them (scan_tiles' ColdT).
 struct ColdFields {
@@ -455,7 +467,7 @@ struct ColdInPlanT {
 // the bytes 1..15, rarest first; then what is left of the far ones; fifteen in all, the first-phase bytes left out - with the
 // rarity classes the plan's filter bytes were chosen by (`cls`: the haystacks' own, else the static four).  Only the ORDER of the
 // checks depends on the classes; the dwords of the exact compare are the needle's bytes.
-__global__ void __launch_bounds__(kBlock) batch_cold_kernel(const BatchArgs a, const BatchDesc *__restrict__ descs, uint64_t count,
+SS_BATCH_KERNEL_LINKAGE __global__ void __launch_bounds__(kBlock) batch_cold_kernel(const BatchArgs a, const BatchDesc *__restrict__ descs, uint64_t count,
                                                              BatchCold *colds, const uint8_t *cls, int find)
 {
     __shared__ uint8_t s_class[256];
@@ -822,7 +834,8 @@ scan_batched_plan_kernel(const BatchArgs a, const BatchDesc *__restrict__ descs,
 // The shape of the reference's short-haystack loop (bench/benches/i386.rs:118-129, tests/i386.rs:46-59:
 // 10.5 M word-in-word searches of <= 24 bytes each): far too small for a workgroup per problem.  Each
 // lane runs the same two-byte filter + compare sequentially over its few candidate offsets.
-__global__ void __launch_bounds__(kBlock) scan_pairs_kernel(const BatchArgs a, uint64_t count)
+#ifndef SS_BATCH_COLD_KERNEL_ONLY
+SS_BATCH_KERNEL_LINKAGE __global__ void __launch_bounds__(kBlock) scan_pairs_kernel(const BatchArgs a, uint64_t count)
 {
     const uint64_t prob = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (prob >= count) return;
@@ -847,5 +860,6 @@ __global__ void __launch_bounds__(kBlock) scan_pairs_kernel(const BatchArgs a, u
     }
     a.found[prob] = result;
 }
+#endif
 
 }  // namespace ss

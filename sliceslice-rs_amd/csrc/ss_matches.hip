@@ -13,68 +13,13 @@
 
 #include "../../include/sliceslice_hip_matches.h"
 #include "matches_launch.hpp"
+#include "matches_scratch.hpp"
 
 namespace ssh {
 namespace {
 
-// ---- call-owned scratch ---------------------------------------------------------------------------------------------------
-// The workgroup counts, their prefix and the total of one call.  A call takes a buffer of its device from a free list (or
-// allocates one) and hands it back once its stream wait has returned, so two calls in flight - two threads, two streams - never
-// share one.  A call that fails keeps its buffer out of the list (work it enqueued may still be running).
-struct Scratch {
-    int dev = -1;
-    uint8_t *d = nullptr;
-    size_t bytes = 0;
-    uint64_t *h = nullptr;      // pinned: the total, read back
-};
-std::mutex g_scratch_mu;
-std::vector<Scratch> g_scratch_free;
-
-int take_scratch(int dev, size_t bytes, Scratch *out)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_scratch_mu);
-        for (size_t k = 0; k < g_scratch_free.size(); ++k) {
-            if (g_scratch_free[k].dev == dev && g_scratch_free[k].bytes >= bytes) {
-                *out = g_scratch_free[k];
-                g_scratch_free.erase(g_scratch_free.begin() + (long)k);
-                return SS_OK;
-            }
-        }
-    }
-    Scratch sc;
-    sc.dev = dev;
-    sc.bytes = (bytes + 4095) & ~(size_t)4095;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc.d), sc.bytes));
-    const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&sc.h), sizeof(uint64_t), hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipFree(sc.d);
-        return fail(SS_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e));
-    }
-    *out = sc;
-    return SS_OK;
-}
-
-struct ScratchLease {
-    Scratch sc;
-    bool done = false;          // the call's stream wait has returned: nothing of it is still using the buffer
-    ~ScratchLease()
-    {
-        if (!done || !sc.d) return;
-        std::lock_guard<std::mutex> lk(g_scratch_mu);
-        g_scratch_free.push_back(sc);
-    }
-};
-
-// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (the rule of ss_scan.hip).
-uint32_t occupancy_pad(int occ, unsigned block)
-{
-    const uint32_t per = (160u * 1024u) / (uint32_t)occ;
-    const uint32_t fixed = (block / ss::kWave) * ss::kNeedleLds;
-    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
-    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
-    return pad;
-}
+// (the call-owned scratch - Scratch, take_scratch, ScratchLease - and occupancy_pad: matches_scratch.hpp, shared with
+// ss_matches_batched.hip)
 
 // One all-matches launch of (searcher, haystack): the Problem (fill_problem, the searcher's own filter bytes) and the shape an
 // untuned search takes - workgroups per CU guessed from the needle, one or two contiguous tiles per workgroup.
@@ -169,7 +114,7 @@ int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, vo
     AllLaunch al;
     if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
     ScratchLease lease;
-    if (int rc = take_scratch(pd->dev, sizeof(uint64_t), &lease.sc)) return rc;
+    if (int rc = take_scratch(pd->dev, sizeof(uint64_t), &lease.sc, st)) return rc;
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
     HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));
     const ss::AllArgs aa = {d_total, nullptr, nullptr, nullptr, 0, ss::kAllCount};
@@ -205,7 +150,7 @@ int ss_find_all_device(const ss_searcher *s, const void *d_haystack, size_t len,
     const uint64_t blocks = al.shape.blocks;
     // [total u64][rank u64 x blocks][count u32 x blocks]
     ScratchLease lease;
-    if (int rc = take_scratch(pd->dev, 8 + blocks * 12, &lease.sc)) return rc;
+    if (int rc = take_scratch(pd->dev, 8 + blocks * 12, &lease.sc, st)) return rc;
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
     uint64_t *d_rank = d_total + 1;
     uint32_t *d_wg = reinterpret_cast<uint32_t *>(d_rank + blocks);

@@ -103,6 +103,12 @@ MATCHES_ABI = {
     "ss_count_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
     "ss_find_all_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_matches_batched.h: every occurrence for a batch of problems - libsliceslice_hip_matches_batched.so only (the
+# matches library's objects plus the batched all-matches scan)
+MATCHES_BATCHED_ABI = {
+    "ss_count_batched": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_batched": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -200,10 +206,12 @@ def _load(path):
     _bind(L, ABI, strict=True)
     _bind(L, SERVICE_ABI, strict=False)
     _bind(L, MATCHES_ABI, strict=False)
+    _bind(L, MATCHES_BATCHED_ABI, strict=False)
     _bind(L, HOOKS_ABI, strict=False)
     L.has_hooks = hasattr(L, "ss_debug_fail_next_scans")
     L.has_service = hasattr(L, "ss_service_start")
     L.has_matches = hasattr(L, "ss_count_device")
+    L.has_matches_batched = hasattr(L, "ss_count_batched")
     return L
 
 
@@ -220,6 +228,7 @@ _tools = None
 _tuning = None
 _service = None
 _matches = None
+_matches_batched = None
 
 
 def tools_lib():
@@ -285,6 +294,32 @@ class matches_build:
         global _lib
         _lib = self._saved
         return False
+
+
+class matches_batched_build:
+    """``with ss.matches_batched_build():`` - inside the block ``lib()`` is libsliceslice_hip_matches_batched.so: every function of
+    the matches library (so ``count`` / ``find_all`` of searchers created inside work too) plus ``count_batched`` /
+    ``find_all_batched`` (include/sliceslice_hip_matches_batched.h), which must be called inside the block."""
+
+    def __enter__(self):
+        global _lib, _matches_batched
+        if _matches_batched is None:
+            _matches_batched = _load(_build.build_matches_batched())
+        self._saved, _lib = _lib, _matches_batched
+        return _matches_batched
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = self._saved
+        return False
+
+
+def _matches_batched_lib():
+    L = lib()
+    if not getattr(L, "has_matches_batched", False):
+        raise SlicesliceError(SS_ERR_ARGUMENT, "count_batched / find_all_batched are not part of this library: they live in "
+                                               "libsliceslice_hip_matches_batched.so - call them inside `with ss.matches_batched_build():`")
+    return L
 
 
 def _matches_lib(L):
@@ -1117,6 +1152,48 @@ def find_batched(haystacks, hay_off, needles, needle_off, stream=None, hay_range
     st = stream if stream is not None else _current_stream_handle()
     _check(lib().ss_find_batched(haystacks.data_ptr(), hb, he, needles.data_ptr(), nb, ne, count, st, pos.data_ptr()))
     return pos                                      # SS_NPOS (all ones) reads as -1
+
+
+def count_batched(haystacks, hay_off, needles, needle_off, stream=None, hay_ranges=None, needle_ranges=None):
+    """(Overlapping) occurrences of needle i in haystack i for many problems in one call (ss_count_batched; inside
+    ``with ss.matches_batched_build():``).  Arguments as search_batched.  Enqueue only; returns an int64 device tensor."""
+    import torch
+    L = _matches_batched_lib()
+    hb, he, count = _ranges(hay_off, *(hay_ranges or (None, None)))
+    nb, ne, ncount = _ranges(needle_off, *(needle_ranges or (None, None)))
+    assert count == ncount
+    counts = torch.empty(count, dtype=torch.int64, device=haystacks.device)
+    st = stream if stream is not None else _current_stream_handle()
+    _check(L.ss_count_batched(haystacks.data_ptr(), hb, he, needles.data_ptr(), nb, ne, count, st, counts.data_ptr()), L)
+    return counts
+
+
+def find_all_batched(haystacks, hay_off, needles, needle_off, stream=None, hay_ranges=None, needle_ranges=None, capacity=None):
+    """Every (overlapping) occurrence of needle i in haystack i for many problems, in CSR form (ss_find_all_batched; inside
+    ``with ss.matches_batched_build():``): ``(counts, row_begin, offsets)`` - int64 device tensors of count, count + 1 and
+    min(total, capacity) entries; ``offsets[row_begin[i]:row_begin[i + 1]]`` are problem i's offsets relative to its own haystack,
+    ascending (rows beyond ``capacity`` are cut).  capacity=None: counted first, then exactly that many.  Waits for the stream."""
+    import torch
+    L = _matches_batched_lib()
+    hb, he, count = _ranges(hay_off, *(hay_ranges or (None, None)))
+    nb, ne, ncount = _ranges(needle_off, *(needle_ranges or (None, None)))
+    assert count == ncount
+    dev = haystacks.device
+    counts = torch.empty(count, dtype=torch.int64, device=dev)
+    rows = torch.empty(count + 1, dtype=torch.int64, device=dev)
+    st = stream if stream is not None else _current_stream_handle()
+    total = _u64(0)
+
+    def call(out, cap):
+        _check(L.ss_find_all_batched(haystacks.data_ptr(), hb, he, needles.data_ptr(), nb, ne, count, st,
+                                     counts.data_ptr() if count else None, rows.data_ptr(), out.data_ptr() if cap else None, int(cap),
+                                     ctypes.byref(total)), L)
+    if capacity is None:
+        call(None, 0)
+        capacity = total.value
+    out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+    call(out, capacity)
+    return counts, rows, out[:min(int(capacity), total.value)]
 
 
 def search_file(searcher, path):

@@ -2,7 +2,9 @@
 """./grep_hip.py <needle> <file> [--count | --offsets] - the reference's examples/grep.rs:42-56 with the "hip"
 backend: map the file, build one searcher, one search_in, print the boolean.
   --count    grep -c style: the number of (overlapping) occurrences (libsliceslice_hip_matches.so, ss_count_device)
-  --offsets  grep -b -o style: one byte offset per line, ascending (ss_find_all_device)"""
+  --offsets  grep -b -o style: one byte offset per line, ascending (ss_find_all_device)
+./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
+per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched)."""
 import os
 import sys
 
@@ -10,9 +12,38 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sliceslice_rs_amd as ss  # noqa: E402
 
 
+def count_patterns(patterns, filename):
+    """One count_batched call: every pattern against the whole file (aliased haystack ranges)."""
+    import numpy as np
+    import torch
+    data = np.fromfile(filename, dtype=np.uint8)
+    blob = np.frombuffer(b"".join(patterns) + b"\x00", dtype=np.uint8).copy()
+    cuts = np.cumsum([0] + [len(p) for p in patterns]).astype(np.int64)
+    with ss.matches_batched_build():
+        hb = torch.zeros(len(patterns), dtype=torch.int64, device="cuda")
+        he = torch.full((len(patterns),), data.size, dtype=torch.int64, device="cuda")
+        counts = ss.count_batched(torch.from_numpy(data).cuda(), None, torch.from_numpy(blob).cuda(), torch.from_numpy(cuts).cuda(),
+                                  hay_ranges=(hb, he))
+        return counts.cpu().tolist()
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    flags = {a for a in sys.argv[1:] if a.startswith("--")}
+    argv, patterns = [], []
+    it = iter(sys.argv[1:])
+    for a in it:
+        if a == "-e":
+            patterns.append(next(it).encode())
+        elif a == "-f":
+            patterns += [l for l in open(next(it), "rb").read().split(b"\n") if l]
+        else:
+            argv.append(a)
+    args = [a for a in argv if not a.startswith("--")]
+    flags = {a for a in argv if a.startswith("--")}
+    if patterns:
+        if len(args) != 1 or flags != {"--count"}:
+            raise SystemExit("./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file>")
+        sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
+        return
     if len(args) < 2 or flags - {"--count", "--offsets", "--rare-position"}:
         raise SystemExit("./grep_hip.py <needle> <file> [--count | --offsets]")
     needle, filename = args[0].encode(), args[1]
