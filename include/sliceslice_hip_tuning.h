@@ -104,7 +104,7 @@ SS_API int ss_debug_plan_filter(const ss_batch_plan *p, size_t problem, uint32_t
  * out[4] = 1 if the next ss_batch_plan_run takes the second layout. */
 SS_API int ss_debug_plan_layout(const ss_batch_plan *p, uint32_t out[5]);
 
-/* A plan's ready-made cold part of `problem` (batched_kernels.hpp, BatchCold): out[0] = bytes in the second-level schedule, out[1] =
+/* A plan's ready-made cold part of `problem` (batched_types.hpp, BatchCold): out[0] = bytes in the second-level schedule, out[1] =
  * exact_len (bytes of the in-register compare | bytes in front of the first filter byte << 8; 0: the needle is too long for it),
  * out[2..5] = the schedule's indices (relative to the first filter byte), one byte each, low dword first; out[6..9] = the needle's
  * bytes at those indices; out[10..13] = the needle's dwords for the compare. */

@@ -45,8 +45,8 @@ _KERNEL_SOURCES = ["scan_inst_u4_nt1.hip", "scan_inst_find_nt1.hip"]
 _SOURCES = _HOST_SOURCES + _KERNEL_SOURCES
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
-_HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
-            "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "batched_all_kernels.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+_HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
+            "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_service.h"),

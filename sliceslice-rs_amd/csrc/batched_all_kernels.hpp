@@ -1,30 +1,25 @@
 // batched_all_kernels.hpp - every occurrence for MANY (needle, haystack) problems in one grid (ss_count_batched /
 // ss_find_all_batched, include/sliceslice_hip_matches_batched.h): the all-matches scan (scan_tiles<..., ALL = true>,
-// scan_kernels.hpp) joined to the batched machinery (BatchDesc, BatchCold, plan_one, batch_cold_kernel: batched_kernels.hpp).
+// scan_kernels.hpp) joined to the batched machinery (BatchDesc, BatchCold, plan_one, ColdInPlanT: batched_types.hpp; batch_cold_kernel of ss_batched.hip).
 // Included by scan_inst_all_batched.hip only - libsliceslice_hip_matches_batched.so, none of the other libraries.
 //
 //   batch_all_plan_kernel     one lane per problem: the descriptor (plan_one, static byte classes), the initial count of a count
 //                             call - 0, or len + 1 for the empty needle: no memset launch - and the empty needle's len + 1 where
 //                             the scan grid finds it
-//   batch_cold_kernel         (batched_kernels.hpp, as it is) one lane per problem: the cold part ready-made, as plans have it.
+//   batch_cold_kernel         (ss_batched.hip's, through launch_batch_cold) one lane per problem: the cold part ready-made, as plans have it.
 //                             The all-matches mode is closed to LAZY_ORDER - no wave builds a schedule - so every problem gets one.
 //   scan_all_batched_kernel   count x slices workgroups, PROBLEM-MAJOR (w = problem * slices + slice), slice s the CONTIGUOUS tiles
 //                             [s * per, (s + 1) * per) of its problem: workgroup order is (problem, address) order, so the
 //                             exclusive prefix sum of the workgroup counts is every workgroup's rank in the CSR output and the
 //                             rows come out sorted with no sort.  One scalar load of the 64-byte descriptor, the hot Problem
-//                             fields as scan_batched_plan_kernel builds them, then the scan: no state word, no polls, no early
+//                             fields (pin_hot_fields, hot_problem: as scan_batched_plan_kernel), then the scan: no state word, no polls, no early
 //                             exit, no PlanState.
-//   prefix64_kernel           exclusive prefix sum of 64-bit workgroup counts (one workgroup, as scan_inst_all.hip's prefix_kernel)
+//   prefix_kernel<uint64_t>   (prefix_kernel.hpp) exclusive prefix sum of the 64-bit workgroup counts, one workgroup
 //   batch_rows_kernel         one lane per problem: d_row_begin and d_counts from the ranks
 #pragma once
 #include "scan_kernels.hpp"
 #include "matches_batched_launch.hpp"        // (the modes: kBatchedAllCount / ...CountPerWorkgroup / ...Emit)
-// batched_kernels.hpp defines its non-template kernels with external linkage for ss_batched.hip, which is linked into the same
-// library: here batch_cold_kernel, the one this unit launches, gets internal linkage - a copy of its own - and the others are left
-// out; the product's objects stay as they are.
-#define SS_BATCH_KERNEL_LINKAGE static
-#define SS_BATCH_COLD_KERNEL_ONLY 1
-#include "batched_kernels.hpp"
+#include "batched_types.hpp"
 
 namespace ss {
 
@@ -63,36 +58,6 @@ __global__ void __launch_bounds__(kBlock) batch_all_plan_kernel(const BatchArgs 
     if (counts) counts[prob] = empty;
 }
 
-// The cold part of a problem, ready-made by batch_cold_kernel: ColdInPlanT<false> without an output pointer and a tally.
-struct ColdAllBatched {
-    static constexpr bool kHasOrder = true;
-    static constexpr bool kMaybeOrder = false;
-    const BatchDesc *dp;
-    const BatchCold *cp;
-    const uint8_t *needles;
-    __device__ __forceinline__ ColdFields operator()() const
-    {
-        const BatchDesc *q = dp;
-        const BatchCold *c = cp;
-        __asm__ volatile("" : "+s"(q), "+s"(c));    // opaque: the loads stay in the cold path
-        ColdFields f;
-        f.hay = q->base + (q->shifts & 15) - q->anchor;
-        f.needle = needles + q->needle_off;
-        f.n = q->n;
-        f.end = q->end;
-        f.norder = c->norder;
-        f.exact_len = c->exact_len;
-        f.order_idx[0] = c->order_idx[0]; f.order_idx[1] = c->order_idx[1];
-        f.order_val[0] = c->order_val[0]; f.order_val[1] = c->order_val[1];
-        f.tail16[0] = c->tail16[0]; f.tail16[1] = c->tail16[1]; f.tail16[2] = c->tail16[2]; f.tail16[3] = c->tail16[3];
-        f.host_flag = nullptr;
-        f.tally = nullptr;
-        f.far_off = 0;
-        f.ready = 1;
-        return f;
-    }
-};
-
 // A lane counts in 32 bits (AllTiles::lane_count) and holds at most 31 matches per piece - its own 16 offsets and, with the exact
 // compare, up to 15 flags handed over from the next lane - so at most 124 per tile (U = 4): the scan of a slice goes in runs of at
 // most kAllRunTiles tiles (4 GiB of haystack), between which the lane's count moves into 64 bits.  (No test scans a slice of more
@@ -118,12 +83,7 @@ __global__ void __launch_bounds__(kBlock) scan_all_batched_kernel(const BatchedA
     const uint32_t prob = w / aa.nslices, slice = w - prob * aa.nslices;
     const BatchDesc *dp = aa.descs + prob;
     BatchDesc d = *dp;
-    {
-        // the hot fields pinned in scalar registers in front of the kernel's first store (see scan_batched_plan_kernel)
-        uint64_t base = reinterpret_cast<uint64_t>(d.base);
-        __asm__ volatile("" : "+s"(base), "+s"(d.end), "+s"(d.nchunks_all), "+s"(d.per), "+s"(d.bytes), "+s"(d.shifts));
-        d.base = reinterpret_cast<const uint8_t *>(base);
-    }
+    pin_hot_fields(d);                              // in front of the kernel's first store
     const uint32_t eff = (uint32_t)(d.per >> 32), per = (uint32_t)d.per;
     constexpr bool emit = EMIT;
     uint64_t rank = 0;
@@ -149,30 +109,17 @@ __global__ void __launch_bounds__(kBlock) scan_all_batched_kernel(const BatchedA
     const uint64_t t0 = (uint64_t)slice * per;
     const uint64_t te = t0 + per < ntiles ? t0 + per : ntiles;
     Problem pr;                                     // hot fields only; the cold ones are re-read from the descriptor
-    pr.base = d.base;
-    pr.nchunks_all = d.nchunks_all;
-    pr.npieces = npieces;
-    pr.d = 0;
-    pr.find_base = 0;
-    pr.mis = mis;
-    pr.r = (d.shifts >> 4) & 3;
-    pr.n0x4 = 0x01010101u * (d.bytes & 0xFF);
-    pr.nlx4 = 0x01010101u * ((d.bytes >> 8) & 0xFF);
-    pr.n3x4 = 0x01010101u * ((d.bytes >> 16) & 0xFF);
-    pr.r3 = (d.shifts >> 8) & 3;
-    pr.q3 = (d.shifts >> 10) & 3;
-    pr.epoch = 1;
-    pr.flags = 0;
-    pr.q = (d.shifts >> 6) & 3;
-    const ColdAllBatched cold = {dp, aa.colds + prob, aa.needles};
+    hot_problem(d, mis, npieces, pr);
+    // the cold part ready-made by batch_cold_kernel, as plans have it; no state word, so no output pointer and no tally
+    const ColdInPlanT<false> cold = {dp, aa.colds + prob, aa.needles, nullptr, nullptr};
     AllTiles at = {0u, emit, rank, aa.out, aa.capacity, s_wave};
     uint64_t mine = 0;
     for (uint64_t t = t0; t < te; t += kAllRunTiles) {
         const uint64_t tr = t + kAllRunTiles < te ? t + kAllRunTiles : te;
         at.lane_count = 0;
         // single stream, non-temporal loads; the second byte's window is run-time data (kQDynamic)
-        if ((d.bytes >> 24) & 1) scan_tiles<0, 0, true, U, 1, false, false, false, ColdAllBatched, true>(pr, cold, s_needle, t, 1, tr, &at);
-        else scan_tiles<kQDynamic, 0, false, U, 1, false, false, false, ColdAllBatched, true>(pr, cold, s_needle, t, 1, tr, &at);
+        if ((d.bytes >> 24) & 1) scan_tiles<0, 0, true, U, 1, false, false, false, ColdInPlanT<false>, true>(pr, cold, s_needle, t, 1, tr, &at);
+        else scan_tiles<kQDynamic, 0, false, U, 1, false, false, false, ColdInPlanT<false>, true>(pr, cold, s_needle, t, 1, tr, &at);
         mine += at.lane_count;
     }
     if (emit) return;
@@ -187,32 +134,6 @@ __global__ void __launch_bounds__(kBlock) scan_all_batched_kernel(const BatchedA
         if (aa.mode == kBatchedAllCountPerWorkgroup) aa.wg_count[w] = sum;
         else if (sum != 0) __hip_atomic_fetch_add(aa.counts + prob, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-// Exclusive prefix sum of n 64-bit workgroup counts into rank[], and their total.  One workgroup, as prefix_kernel of
-// scan_inst_all.hip (which takes 32-bit counts): thread t sums a contiguous run, the runs' sums are scanned in LDS.
-constexpr int kPrefix64Threads = 1024;
-__global__ void __launch_bounds__(kPrefix64Threads) prefix64_kernel(const uint64_t *count, uint64_t n, uint64_t *rank, uint64_t *total)
-{
-    __shared__ uint64_t s_run[kPrefix64Threads];
-    const uint64_t per = (n + kPrefix64Threads - 1) / kPrefix64Threads;
-    const uint64_t b0 = (uint64_t)threadIdx.x * per, b = b0 < n ? b0 : n, e = b + per < n ? b + per : n;
-    uint64_t sum = 0;
-    for (uint64_t k = b; k < e; ++k) sum += count[k];
-    s_run[threadIdx.x] = sum;
-    __syncthreads();
-    for (int k = 1; k < kPrefix64Threads; k <<= 1) {           // Hillis-Steele inclusive scan of the run sums
-        const uint64_t v = threadIdx.x >= (unsigned)k ? s_run[threadIdx.x - k] : 0ull;
-        __syncthreads();
-        s_run[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t r = s_run[threadIdx.x] - sum;
-    for (uint64_t k = b; k < e; ++k) {
-        rank[k] = r;
-        r += count[k];
-    }
-    if (threadIdx.x == kPrefix64Threads - 1) *total = s_run[threadIdx.x];
 }
 
 // One lane per problem (and one for the end): row_begin[p] = rank of the problem's first workgroup, row_begin[count] = the total,

@@ -1,5 +1,5 @@
 // matches_batched_launch.hpp - host-side entry points of the batched all-matches kernels (defined in scan_inst_all_batched.hip,
-// used by ss_matches_batched.hip).  The descriptor types stay inside the kernels' translation unit: the host sees bytes.
+// used by ss_matches_batched.hip).  The descriptors and cold records stay inside the kernels' translation unit: the host sees bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -7,18 +7,13 @@
 
 namespace ss {
 
-struct BatchedAllRanges {
-    const void *haystacks;
-    const uint64_t *hay_begin, *hay_end;
-    const void *needles;
-    const uint64_t *needle_begin, *needle_end;
-};
+struct BatchArgs;               // batched_types.hpp: the batch as the caller names it (ssh::fill_batch_args)
 constexpr size_t kBatchedAllDescBytes = 64, kBatchedAllColdBytes = 64;     // per problem: BatchDesc, BatchCold
 constexpr uint32_t kBatchedAllCount = 0, kBatchedAllCountPerWorkgroup = 1, kBatchedAllEmit = 2;
 
 // Descriptors and cold parts of `count` problems for a scan grid of `nslices` workgroups per problem (slices no shorter than
 // `min_tiles` tiles); `counts` (may be null) takes every problem's initial count: 0, or len + 1 for the empty needle.
-hipError_t launch_batched_all_plan(const BatchedAllRanges &r, uint64_t count, void *descs, void *colds, uint32_t nslices, uint32_t min_tiles,
+hipError_t launch_batched_all_plan(const BatchArgs &a, uint64_t count, void *descs, void *colds, uint32_t nslices, uint32_t min_tiles,
                                    uint64_t *counts, hipStream_t st);
 struct BatchedAllScan {
     const void *descs, *colds;

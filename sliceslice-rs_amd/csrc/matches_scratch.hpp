@@ -84,14 +84,4 @@ struct ScratchLease {
     }
 };
 
-// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (the rule of ss_scan.hip).
-inline uint32_t occupancy_pad(int occ, unsigned block)
-{
-    const uint32_t per = (160u * 1024u) / (uint32_t)occ;
-    const uint32_t fixed = (block / ss::kWave) * ss::kNeedleLds;
-    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
-    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
-    return pad;
-}
-
 }  // namespace ssh

@@ -1,8 +1,9 @@
 // scan_inst_all.hip - the all-matches kernels (scan_all_kernel, scan_kernels.hpp) and their small helpers: one scan kernel per
 // (Q, MODE, one-byte) combination that find() has - 4 Q x MODE 0, 4 Q x MODE 2, one-byte: 9 - plus the prefix sum of the
-// workgroup counts and the empty needle's fill.  Compiled into libsliceslice_hip_matches.so only (ss_matches.hip is the host side).
+// workgroup counts (prefix_kernel.hpp) and the empty needle's fill.  Compiled into libsliceslice_hip_matches.so only (ss_matches.hip is the host side).
 #include "scan_launch.hpp"
 #include "matches_launch.hpp"
+#include "prefix_kernel.hpp"
 
 namespace ss {
 
@@ -13,34 +14,6 @@ void launch_all_one(const Problem &pr, const Shape &sh, hipStream_t st, const Al
 {
     const uint32_t dyn_lds = sh.lds_pad + (sh.block / kWave) * kNeedleLds;   // one needle slice per wave
     scan_all_kernel<Q, MODE, ONE_BYTE><<<dim3(sh.blocks), dim3(sh.block), dyn_lds, st>>>(pr, aa, sh.tpb);
-}
-
-// Exclusive prefix sum of the n workgroup counts (u32) into rank[] (u64), and their total.  One workgroup: thread t sums a
-// contiguous run of the counts, the runs' sums are scanned in LDS, and every thread writes the ranks of its run.  The counts of a
-// 1 GiB haystack are 256 KiB.
-constexpr int kPrefixThreads = 1024;
-__global__ void __launch_bounds__(kPrefixThreads) prefix_kernel(const uint32_t *count, uint64_t n, uint64_t *rank, uint64_t *total)
-{
-    __shared__ uint64_t s_sum[kPrefixThreads];
-    const uint64_t per = (n + kPrefixThreads - 1) / kPrefixThreads;
-    const uint64_t b = (uint64_t)threadIdx.x * per, e = b + per < n ? b + per : n;
-    uint64_t sum = 0;
-    for (uint64_t k = b; k < e; ++k) sum += count[k];
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    // Hillis-Steele inclusive scan of the run sums
-    for (int k = 1; k < kPrefixThreads; k <<= 1) {
-        const uint64_t v = threadIdx.x >= (unsigned)k ? s_sum[threadIdx.x - k] : 0ull;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint64_t r = s_sum[threadIdx.x] - sum;
-    for (uint64_t k = b; k < e; ++k) {
-        rank[k] = r;
-        r += count[k];
-    }
-    if (threadIdx.x == kPrefixThreads - 1) *total = s_sum[threadIdx.x];
 }
 
 // The empty needle: offsets 0 .. count - 1
@@ -70,7 +43,7 @@ bool launch_scan_all(const Problem &pr, int q, int mode, bool one_byte, const Sh
 
 hipError_t launch_prefix(const uint32_t *count, uint64_t n, uint64_t *rank, uint64_t *total, hipStream_t st)
 {
-    prefix_kernel<<<1, kPrefixThreads, 0, st>>>(count, n, rank, total);
+    prefix_kernel<uint32_t><<<1, kPrefixThreads, 0, st>>>(count, n, rank, total);
     return hipGetLastError();
 }
 

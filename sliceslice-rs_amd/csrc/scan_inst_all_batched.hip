@@ -1,33 +1,22 @@
-// scan_inst_all_batched.hip - the batched all-matches kernels (batched_all_kernels.hpp) and their launches: the plan and cold
-// kernels in front of the scan, scan_all_batched_kernel, the 64-bit prefix sum and the rows.  Compiled into
+// scan_inst_all_batched.hip - the batched all-matches kernels (batched_all_kernels.hpp) and their launches: the plan kernel (and
+// ss_batched.hip's cold kernel) in front of the scan, scan_all_batched_kernel, the 64-bit prefix sum and the rows.  Compiled into
 // libsliceslice_hip_matches_batched.so only (ss_matches_batched.hip is the host side).
 #include "batched_all_kernels.hpp"
 #include "matches_batched_launch.hpp"
+#include "prefix_kernel.hpp"
 
 namespace ss {
 
 static_assert(sizeof(BatchDesc) == kBatchedAllDescBytes && sizeof(BatchCold) == kBatchedAllColdBytes, "the host sizes its scratch by these");
 
-hipError_t launch_batched_all_plan(const BatchedAllRanges &r, uint64_t count, void *descs, void *colds, uint32_t nslices, uint32_t min_tiles,
+hipError_t launch_batched_all_plan(const BatchArgs &a, uint64_t count, void *descs, void *colds, uint32_t nslices, uint32_t min_tiles,
                                    uint64_t *counts, hipStream_t st)
 {
-    BatchArgs a;
-    a.haystacks = static_cast<const uint8_t *>(r.haystacks);
-    a.hay_begin = r.hay_begin;
-    a.hay_end = r.hay_end;
-    a.needles = static_cast<const uint8_t *>(r.needles);
-    a.needle_begin = r.needle_begin;
-    a.needle_end = r.needle_end;
-    a.position = nullptr;
-    a.found = nullptr;
-    a.best = nullptr;
     const unsigned blocks = (unsigned)((count + kBlock - 1) / kBlock);
     batch_all_plan_kernel<<<dim3(blocks), dim3(kBlock), 0, st>>>(a, count, static_cast<BatchDesc *>(descs), nslices, min_tiles, counts);
     if (hipError_t e = hipGetLastError()) return e;
     // (static classes, bool-style idle state words: nobody reads them)
-    batch_cold_kernel<<<dim3(blocks), dim3(kBlock), 0, st>>>(a, static_cast<const BatchDesc *>(descs), count, static_cast<BatchCold *>(colds),
-                                                                nullptr, 0);
-    return hipGetLastError();
+    return launch_batch_cold(a, static_cast<const BatchDesc *>(descs), count, static_cast<BatchCold *>(colds), nullptr, 0, st);
 }
 
 hipError_t launch_batched_all_scan(const BatchedAllScan &s, uint64_t count, uint32_t nslices, uint32_t lds_pad, hipStream_t st)
@@ -43,7 +32,7 @@ hipError_t launch_batched_all_scan(const BatchedAllScan &s, uint64_t count, uint
 
 hipError_t launch_prefix64(const uint64_t *count, uint64_t n, uint64_t *rank, uint64_t *total, hipStream_t st)
 {
-    prefix64_kernel<<<1, kPrefix64Threads, 0, st>>>(count, n, rank, total);
+    prefix_kernel<uint64_t><<<1, kPrefixThreads, 0, st>>>(count, n, rank, total);
     return hipGetLastError();
 }
 

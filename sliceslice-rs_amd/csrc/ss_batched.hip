@@ -10,7 +10,6 @@
 #include "batched_kernels.hpp"
 
 namespace ssh {
-namespace {
 
 // Total workgroups aimed at, per CU.  Measured in one process on one buffer (tools/batch_tune.py, profiles/r03/batch_tune_*.jsonl;
 // kernel time: tools/shape_trace.py under rocprofv3): 96 per CU is best or within 1 % of the best on every shape at 1 GiB in
@@ -26,6 +25,58 @@ constexpr uint32_t kPlanMinTiles = 2;       // shortest slice worth a workgroup,
 constexpr uint32_t kPlanMinTilesCounted = 8;
 constexpr uint32_t kPlanTilesPerWg = 10;
 constexpr uint32_t kPlanTilesPerWgLong = 4, kPlanMinTilesLong = 4;   // problems of more than 80 tiles (1.25 MiB): see ss_batch_plan_create
+
+bool stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    return capturing;
+}
+
+int fill_batch_args(ss::BatchArgs *a, const void *d_haystacks, const uint64_t *d_hay_begin, const uint64_t *d_hay_end,
+                    const void *d_needles, const uint64_t *d_needle_begin, const uint64_t *d_needle_end, const uint64_t *d_position)
+{
+    if (!d_hay_begin || !d_hay_end || !d_needle_begin || !d_needle_end) return fail(SS_ERR_ARGUMENT, "NULL argument");
+    a->haystacks = static_cast<const uint8_t *>(d_haystacks);
+    a->hay_begin = d_hay_begin;
+    a->hay_end = d_hay_end;
+    a->needles = static_cast<const uint8_t *>(d_needles);
+    a->needle_begin = d_needle_begin;
+    a->needle_end = d_needle_end;
+    a->position = d_position;
+    a->found = nullptr;
+    a->best = nullptr;
+    return SS_OK;
+}
+
+// The grid of a batch: the haystack lengths live on the device, so it is sized from the problem COUNT - kPlanWgsPerCu
+// workgroups per CU in total, i.e. `slices` workgroups per problem.  The price of being wrong is small: a surplus slice costs
+// one scalar round trip, and a slice as short as kPlanMinTiles tiles is worth a workgroup because nothing but that load stands
+// in front of its first haystack byte.
+// The limit on `count` keeps the grid within gridDim.x whatever the device: count * ceil(T / count) < T + count < 2^31 for the
+// T = kPlanWgsPerCu x CUs of any device, so the loop below only ever turns for a hook build's SLICESLICE_BATCH_WGS, and a caller
+// that refused count * slices > 0x7fffffff instead would refuse nothing that gets here: the two guards agree.
+int batch_shape(int dev, size_t count, BatchShape *out, bool counted)
+{
+    DeviceInfo di;
+    if (int rc = device_info(dev, &di)) return rc;
+    if (count > 0x3fffffffull) return fail(SS_ERR_ARGUMENT, "too many problems");
+    uint64_t wg_target = (uint64_t)di.cus * kPlanWgsPerCu;
+    uint32_t min_tiles = counted ? kPlanMinTilesCounted : kPlanMinTiles;
+#ifdef SS_TEST_HOOKS
+    if (const char *e = getenv("SLICESLICE_BATCH_WGS")) { const long v = atol(e); if (v > 0) wg_target = (uint64_t)v; }
+    if (const char *e = getenv("SLICESLICE_BATCH_MIN_TILES")) { const long v = atol(e); if (v > 0) min_tiles = (uint32_t)v; }
+#endif
+    uint64_t slices = (wg_target + count - 1) / count;
+    if (slices < 1) slices = 1;
+    while (slices > 1 && (uint64_t)count * slices > 0x7fffffffull) --slices;   // gridDim.x
+    out->slices = (uint32_t)slices;
+    out->min_tiles = min_tiles;
+    return SS_OK;
+}
+
+namespace {
 
 // Descriptor scratch of the unplanned calls: one grow-only device buffer per (device, stream), kept for the life of the process.
 // Launches on one stream execute in order, so a buffer that belongs to the stream can be reused by the next call on that
@@ -106,52 +157,7 @@ uint32_t batch_lds_pad()
 #ifdef SS_TEST_HOOKS
     if (const char *e = getenv("SLICESLICE_BATCH_OCC")) { const int v = atoi(e); if (v >= 1 && v <= 8) occ = v; }
 #endif
-    const uint32_t per = (160u * 1024u) / (uint32_t)occ, fixed = ss::kWavesPerBlock * ss::kNeedleLds;
-    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
-    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
-    return pad;
-}
-
-int fill_batch_args(ss::BatchArgs *a, const void *d_haystacks, const uint64_t *d_hay_begin, const uint64_t *d_hay_end,
-                    const void *d_needles, const uint64_t *d_needle_begin, const uint64_t *d_needle_end, const uint64_t *d_position)
-{
-    if (!d_hay_begin || !d_hay_end || !d_needle_begin || !d_needle_end) return fail(SS_ERR_ARGUMENT, "NULL argument");
-    a->haystacks = static_cast<const uint8_t *>(d_haystacks);
-    a->hay_begin = d_hay_begin;
-    a->hay_end = d_hay_end;
-    a->needles = static_cast<const uint8_t *>(d_needles);
-    a->needle_begin = d_needle_begin;
-    a->needle_end = d_needle_end;
-    a->position = d_position;
-    a->found = nullptr;
-    a->best = nullptr;
-    return SS_OK;
-}
-
-// The grid of a batch: the haystack lengths live on the device, so it is sized from the problem COUNT - kPlanWgsPerCu
-// workgroups per CU in total, i.e. `slices` workgroups per problem.  The price of being wrong is small: a surplus slice costs
-// one scalar round trip, and a slice as short as kPlanMinTiles tiles is worth a workgroup because nothing but that load stands
-// in front of its first haystack byte.
-struct BatchShape {
-    uint32_t slices, min_tiles;
-};
-int batch_shape(int dev, size_t count, BatchShape *out, bool counted = false)
-{
-    DeviceInfo di;
-    if (int rc = device_info(dev, &di)) return rc;
-    if (count > 0x3fffffffull) return fail(SS_ERR_ARGUMENT, "too many problems");
-    uint64_t wg_target = (uint64_t)di.cus * kPlanWgsPerCu;
-    uint32_t min_tiles = counted ? kPlanMinTilesCounted : kPlanMinTiles;
-#ifdef SS_TEST_HOOKS
-    if (const char *e = getenv("SLICESLICE_BATCH_WGS")) { const long v = atol(e); if (v > 0) wg_target = (uint64_t)v; }
-    if (const char *e = getenv("SLICESLICE_BATCH_MIN_TILES")) { const long v = atol(e); if (v > 0) min_tiles = (uint32_t)v; }
-#endif
-    uint64_t slices = (wg_target + count - 1) / count;
-    if (slices < 1) slices = 1;
-    while (slices > 1 && (uint64_t)count * slices > 0x7fffffffull) --slices;   // gridDim.x
-    out->slices = (uint32_t)slices;
-    out->min_tiles = min_tiles;
-    return SS_OK;
+    return occupancy_pad(occ, ss::kBlock);
 }
 
 // `cls` (may be null): the 256 rarity classes batch_sample_kernel derived from the haystacks' own bytes - the filter bytes are
@@ -268,11 +274,9 @@ int launch_batched(const ss::BatchArgs &a, size_t count, hipStream_t st)
 {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(st))
         return fail(SS_ERR_ARGUMENT, "ss_search_batched / ss_find_batched keep per-stream scratch and cannot be captured into a hipGraph: "
                                      "build an ss_batch_plan outside the capture and capture ss_batch_plan_run");
-    (void)hipGetLastError();
     BatchShape sh;
     if (int rc = batch_shape(dev, count, &sh)) return rc;
     PlanScratch *ps = plan_scratch_acquire(dev, st, count);
@@ -298,6 +302,17 @@ int launch_batched(const ss::BatchArgs &a, size_t count, hipStream_t st)
 
 }  // namespace
 }  // namespace ssh
+
+namespace ss {
+
+hipError_t launch_batch_cold(const BatchArgs &a, const BatchDesc *descs, uint64_t count, BatchCold *colds, const uint8_t *cls, int find,
+                             hipStream_t st)
+{
+    batch_cold_kernel<<<dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st>>>(a, descs, count, colds, cls, find);
+    return hipGetLastError();
+}
+
+}  // namespace ss
 
 using namespace ssh;
 
@@ -372,10 +387,7 @@ int ss_batch_plan_create(const void *d_haystacks, const uint64_t *d_hay_begin, c
     *out = nullptr;
     if (count == 0) return fail(SS_ERR_ARGUMENT, "a plan needs at least one problem");
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(SS_ERR_ARGUMENT, "ss_batch_plan_create allocates and waits: call it outside the stream capture");
-    (void)hipGetLastError();
+    if (stream_is_capturing(st)) return fail(SS_ERR_ARGUMENT, "ss_batch_plan_create allocates and waits: call it outside the stream capture");
     ss_batch_plan *p = new (std::nothrow) ss_batch_plan;
     if (!p) return fail(SS_ERR_NOMEM, "out of memory");
     p->count = count;
@@ -438,10 +450,8 @@ int ss_batch_plan_create(const void *d_haystacks, const uint64_t *d_hay_begin, c
             const uint32_t most = seen.max_slices;
             p->shape.slices = most < 1 ? 1 : (most < p->shape.slices ? most : p->shape.slices);
             // the cold part of every problem (second-level schedule, the needle's dwords): once, here, instead of by every wave that
-            // meets a candidate (batched_kernels.hpp, BatchCold)
-            ss::batch_cold_kernel<<<dim3((unsigned)((count + ss::kBlock - 1) / ss::kBlock)), dim3(ss::kBlock), 0, st>>>(p->args, p->descs(), (uint64_t)count,
-                                                                                                                        p->colds(), cls, p->find ? 1 : 0);
-            e = hipGetLastError();
+            // meets a candidate (batched_types.hpp, BatchCold)
+            e = ss::launch_batch_cold(p->args, p->descs(), (uint64_t)count, p->colds(), cls, p->find ? 1 : 0, st);
             // the runs' state: every problem's two state words idle (bool: 0, find: all ones), the control word naming no run
             if (e == hipSuccess) e = hipMemsetAsync(p->states(), p->find ? 0xFF : 0, count * sizeof(ss::PlanState), st);
             if (e == hipSuccess) e = hipMemsetAsync(p->ctl(), 0, sizeof(ss::PlanCtl), st);

@@ -33,6 +33,10 @@
 #include "../../include/sliceslice_hip_tuning.h"
 #include "scan_filters.hpp"
 
+namespace ss {
+struct BatchArgs;                       // batched_types.hpp
+}
+
 namespace ssh {
 
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -275,6 +279,13 @@ struct ProblemShape {
 // `triple` != nullptr: filter bytes chosen for this haystack instead of the searcher's own (all within 16 bytes of the first).
 void fill_problem(const ss_searcher *s, const uint8_t *d_needle, const void *d_hay, size_t len, uint64_t find_base, ss::Problem *out,
                   ProblemShape *shape, const size_t *triple = nullptr);
+// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (160 KiB of LDS).
+uint32_t occupancy_pad(int occ, unsigned block);
+// The launch shape of a scan that has nothing but the needle and the device to go by (no census, no tuning variant):
+// workgroups per CU - six when every filter byte is text-like, else four - and, for `ntiles` tiles in kernel family `mode`, the tiles
+// per workgroup (*tpb; non-zero on entry: given) and the grid.
+int guess_workgroups_per_cu(const ss_searcher *s, const ss::Problem &pr, const ProblemShape &ps);
+int launch_grid(int dev, int mode, uint64_t ntiles, uint64_t *tpb, uint64_t *blocks);
 bool autotune_enabled();          // ss_set_autotune / SLICESLICE_AUTOTUNE (ss_census.hip): off = static choices only, no sampling kernels
 // Builds the Problem for (hay, len) and enqueues the scan.  find == false: *d_sink is an int flag, set to `epoch` by the wave that
 // finds the needle, never cleared.  find == true: *d_sink is a uint64, atomicMin'ed with find_base + offset of every match the grid
@@ -297,6 +308,19 @@ bool spin_for_shard_word(const long long *word, int epoch, double estimate_us, i
 // found), and find()'s minimum into its pinned mirror (pair: {offset, status}; else the device word is re-armed)
 hipError_t launch_signal_flag(hipStream_t st, const int *d_flag, int epoch, long long *h_word, int pair);
 hipError_t launch_publish_best(hipStream_t st, uint64_t *d_best, uint64_t *h_best, int pair);
+
+// ---- ss_batched.hip ---------------------------------------------------------------------------------------------------
+// What the many-problem calls of other translation units (ss_matches_batched.hip) take from it.
+// True when `st` is being captured into a hipGraph (calls that keep scratch between launches, allocate or wait refuse it).
+bool stream_is_capturing(hipStream_t st);
+// The six range pointers (and `d_position`, may be null) as the kernels' BatchArgs (batched_types.hpp), outputs null.
+int fill_batch_args(ss::BatchArgs *a, const void *d_haystacks, const uint64_t *d_hay_begin, const uint64_t *d_hay_end,
+                    const void *d_needles, const uint64_t *d_needle_begin, const uint64_t *d_needle_end, const uint64_t *d_position);
+// The grid of a batch of `count` problems: `slices` workgroups per problem, none shorter than `min_tiles` tiles.
+struct BatchShape {
+    uint32_t slices, min_tiles;
+};
+int batch_shape(int dev, size_t count, BatchShape *out, bool counted = false);
 
 #ifdef SS_TEST_HOOKS
 bool cross_exit_enabled();        // SLICESLICE_CROSS_EXIT != 0 (hooks builds: the relay's effect is measured by a test)

@@ -18,11 +18,11 @@
 namespace ssh {
 namespace {
 
-// (the call-owned scratch - Scratch, take_scratch, ScratchLease - and occupancy_pad: matches_scratch.hpp, shared with
-// ss_matches_batched.hip)
+// (the call-owned scratch - Scratch, take_scratch, ScratchLease: matches_scratch.hpp, shared with ss_matches_batched.hip)
 
 // One all-matches launch of (searcher, haystack): the Problem (fill_problem, the searcher's own filter bytes) and the shape an
-// untuned search takes - workgroups per CU guessed from the needle, one or two contiguous tiles per workgroup.
+// untuned search takes - workgroups per CU guessed from the needle, one or two contiguous tiles per workgroup (ss_scan.hip:
+// guess_workgroups_per_cu, launch_grid).
 struct AllLaunch {
     ss::Problem pr;
     ss::Shape shape;
@@ -34,28 +34,15 @@ int plan_all(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len,
 {
     ProblemShape ps;
     fill_problem(s, pd->d_needle, d_hay, len, 0, &out->pr, &ps, nullptr);
-    const bool one_byte = ps.one_byte;
-    const size_t fa = ps.fa, position = ps.position, position3 = ps.position3;
-    const bool text_like = !one_byte && ss::byte_rarity_rank(s->needle[fa]) >= 64 && ss::byte_rarity_rank(s->needle[fa + position]) >= 64 &&
-                           ss::byte_rarity_rank(s->needle[fa + position3]) >= 64;
-    const int occ = !one_byte && text_like && out->pr.d == 0 ? 6 : 4;
+    const int occ = guess_workgroups_per_cu(s, out->pr, ps);
     out->mode = out->pr.d == 0 ? 0 : 2;
-    out->one_byte = one_byte;
-    out->q = (int)((position % 16) / 4);
+    out->one_byte = ps.one_byte;
+    out->q = (int)((ps.position % 16) / 4);
     const unsigned block = ss::kBlock;
     const uint64_t per_tile = (block / ss::kWave) * 4;                  // pieces per tile at U = 4
     const uint64_t ntiles = (out->pr.npieces + per_tile - 1) / per_tile;
-    DeviceInfo di;
-    if (int rc = device_info(pd->dev, &di)) return rc;
-    uint64_t tpb = ntiles / ((uint64_t)di.cus * (out->mode == 0 ? 256 : 128));
-    if (tpb > 2) tpb = 2;
-    if (tpb < 1) tpb = 1;
-    uint64_t blocks = (ntiles + tpb - 1) / tpb;
-    while (blocks > 0x7fffffffull) {        // gridDim.x limit
-        tpb *= 2;
-        blocks = (ntiles + tpb - 1) / tpb;
-    }
-    if (blocks < 1) blocks = 1;
+    uint64_t tpb = 0, blocks = 0;
+    if (int rc = launch_grid(pd->dev, out->mode, ntiles, &tpb, &blocks)) return rc;
     out->shape = {(unsigned)blocks, block, tpb, occupancy_pad(occ, block)};
     return SS_OK;
 }

@@ -15,40 +15,27 @@
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_matches_batched.h"
+#include "batched_types.hpp"
 #include "matches_batched_launch.hpp"
 #include "matches_scratch.hpp"
 
 namespace ssh {
 namespace {
 
-// As ss_batched.hip: workgroups aimed at per CU in total, and the shortest slice worth a workgroup (16 KiB tiles).
-constexpr unsigned kAllWgsPerCu = 96;
-constexpr uint32_t kAllMinTiles = 2;
-
 struct BatchedAllCall {
     int dev = 0;
-    uint32_t slices = 1;
-    ss::BatchedAllRanges ranges;
+    BatchShape shape = {1, 1};      // the grid rule of ss_search_batched (batch_shape, ss_batched.hip)
+    ss::BatchArgs args;
 };
 
 int prepare(BatchedAllCall *c, const char *who, const void *d_haystacks, const uint64_t *d_hay_begin, const uint64_t *d_hay_end,
             const void *d_needles, const uint64_t *d_needle_begin, const uint64_t *d_needle_end, size_t count, hipStream_t st)
 {
-    if (!d_hay_begin || !d_hay_end || !d_needle_begin || !d_needle_end) return fail(SS_ERR_ARGUMENT, "NULL argument");
+    if (int rc = fill_batch_args(&c->args, d_haystacks, d_hay_begin, d_hay_end, d_needles, d_needle_begin, d_needle_end, nullptr)) return rc;
     HIP_TRY(hipGetDevice(&c->dev));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    if (stream_is_capturing(st))
         return fail(SS_ERR_ARGUMENT, "%s keeps scratch that later calls take over and cannot be captured into a hipGraph", who);
-    (void)hipGetLastError();
-    DeviceInfo di;
-    if (int rc = device_info(c->dev, &di)) return rc;
-    if (count > 0x3fffffffull) return fail(SS_ERR_ARGUMENT, "too many problems");
-    // count x slices < 96 x CUs + count: within gridDim.x for every count that got here
-    const uint64_t slices = ((uint64_t)di.cus * kAllWgsPerCu + count - 1) / count;
-    if ((uint64_t)count * slices > 0x7fffffffull) return fail(SS_ERR_ARGUMENT, "too many problems for a device of %d compute units", di.cus);
-    c->slices = (uint32_t)slices;
-    c->ranges = {d_haystacks, d_hay_begin, d_hay_end, d_needles, d_needle_begin, d_needle_end};
-    return SS_OK;
+    return batch_shape(c->dev, count, &c->shape);
 }
 
 // four workgroups per CU, as the batched search and the single all-matches scan on random bytes
@@ -75,9 +62,9 @@ int ss_count_batched(const void *d_haystacks, const uint64_t *d_hay_begin, const
     ScratchLease lease;
     if (int rc = take_scratch(c.dev, count * (ss::kBatchedAllDescBytes + ss::kBatchedAllColdBytes), &lease.sc, st)) return rc;
     uint8_t *descs = lease.sc.d, *colds = descs + count * ss::kBatchedAllDescBytes;
-    HIP_TRY(ss::launch_batched_all_plan(c.ranges, count, descs, colds, c.slices, kAllMinTiles, d_counts, st));
+    HIP_TRY(ss::launch_batched_all_plan(c.args, count, descs, colds, c.shape.slices, c.shape.min_tiles, d_counts, st));
     const ss::BatchedAllScan scan = {descs, colds, d_needles, d_counts, nullptr, nullptr, nullptr, 0, ss::kBatchedAllCount};
-    HIP_TRY(ss::launch_batched_all_scan(scan, count, c.slices, lds_pad(), st));
+    HIP_TRY(ss::launch_batched_all_scan(scan, count, c.shape.slices, lds_pad(), st));
     return lease.release_on(st);
 }
 
@@ -98,7 +85,7 @@ int ss_find_all_batched(const void *d_haystacks, const uint64_t *d_hay_begin, co
     BatchedAllCall c;
     if (int rc = prepare(&c, "ss_find_all_batched", d_haystacks, d_hay_begin, d_hay_end, d_needles, d_needle_begin, d_needle_end, count, st))
         return rc;
-    const uint64_t blocks = (uint64_t)count * c.slices;
+    const uint64_t blocks = (uint64_t)count * c.shape.slices;
     // [descriptors][cold parts][total u64][rank u64 x blocks][count u64 x blocks]
     const size_t plan_bytes = count * (ss::kBatchedAllDescBytes + ss::kBatchedAllColdBytes);
     ScratchLease lease;
@@ -106,14 +93,14 @@ int ss_find_all_batched(const void *d_haystacks, const uint64_t *d_hay_begin, co
     uint8_t *descs = lease.sc.d, *colds = descs + count * ss::kBatchedAllDescBytes;
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d + plan_bytes);
     uint64_t *d_rank = d_total + 1, *d_wg = d_rank + blocks;
-    HIP_TRY(ss::launch_batched_all_plan(c.ranges, count, descs, colds, c.slices, kAllMinTiles, nullptr, st));
+    HIP_TRY(ss::launch_batched_all_plan(c.args, count, descs, colds, c.shape.slices, c.shape.min_tiles, nullptr, st));
     const ss::BatchedAllScan counting = {descs, colds, d_needles, nullptr, d_wg, nullptr, nullptr, 0, ss::kBatchedAllCountPerWorkgroup};
-    HIP_TRY(ss::launch_batched_all_scan(counting, count, c.slices, lds_pad(), st));
+    HIP_TRY(ss::launch_batched_all_scan(counting, count, c.shape.slices, lds_pad(), st));
     HIP_TRY(ss::launch_prefix64(d_wg, blocks, d_rank, d_total, st));
-    HIP_TRY(ss::launch_batched_rows(d_rank, d_total, count, c.slices, d_row_begin, d_counts, st));
+    HIP_TRY(ss::launch_batched_rows(d_rank, d_total, count, c.shape.slices, d_row_begin, d_counts, st));
     if (capacity) {
         const ss::BatchedAllScan emitting = {descs, colds, d_needles, nullptr, d_wg, d_rank, d_offsets, capacity, ss::kBatchedAllEmit};
-        HIP_TRY(ss::launch_batched_all_scan(emitting, count, c.slices, lds_pad(), st));
+        HIP_TRY(ss::launch_batched_all_scan(emitting, count, c.shape.slices, lds_pad(), st));
     }
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

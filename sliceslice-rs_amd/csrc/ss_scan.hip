@@ -81,6 +81,58 @@ hipError_t launch_publish_best(hipStream_t st, uint64_t *d_best, uint64_t *h_bes
     return hipGetLastError();
 }
 
+// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (160 KiB of LDS).
+uint32_t occupancy_pad(int occ, unsigned block)
+{
+    const uint32_t per = (160u * 1024u) / (uint32_t)occ;
+    const uint32_t fixed = (block / ss::kWave) * ss::kNeedleLds;
+    // (1 KiB short of the share: the kernels also own a few bytes of static LDS - the completion word's workgroup flag -
+    // and a workgroup's allocation is rounded up to the hardware's granule)
+    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
+    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
+    return pad;
+}
+
+// Workgroups per CU when all there is to go by is the NEEDLE (no census counts; see pick_variant below): every filter byte text-like
+// -> the haystack is presumably text and candidates are to be expected - six, single-stream kernels only; otherwise four.
+int guess_workgroups_per_cu(const ss_searcher *s, const ss::Problem &pr, const ProblemShape &ps)
+{
+    const bool text_like = !ps.one_byte && ss::byte_rarity_rank(s->needle[ps.fa]) >= 64 &&
+                           ss::byte_rarity_rank(s->needle[ps.fa + ps.position]) >= 64 &&
+                           ss::byte_rarity_rank(s->needle[ps.fa + ps.position3]) >= 64;
+    return text_like && pr.d == 0 ? 6 : 4;
+}
+
+constexpr int kAutoTilesPerBlock = 2;    // 32 KiB contiguous per workgroup at U = 4 (profiles/r01/tiles_per_block_sweep.jsonl)
+
+// Tiles per workgroup and grid for `ntiles` tiles on device `dev`, kernel family `mode`.  *tpb != 0: somebody has chosen the tiles
+// per workgroup (a tuning grid, the census); 0: chosen here.
+// Short-lived workgroups: two tiles (32 KiB) each from 2 GiB up (from 1 GiB for filter pairs >= 16 apart), one
+// below.  The hardware dispatcher hands out tiles in address order, so the set of lines in flight
+// stays one narrow, advancing window, and a fresh workgroup issues its loads the moment a slot
+// frees up.  Measured (profiles/r01/tiles_per_block_sweep.jsonl, tiles_1_vs_2.txt; 16-byte needle):
+// 64 GiB 7.40-7.43 TB/s at 2 tiles per workgroup vs 7.28 at 4, 7.21 at 8, 7.11 at 64.  One tile is
+// +2 % at 1 GiB, within +-0.7 % from 4 GiB up (and +1.5 % for one-byte needles), but twice as many
+// workgroups have to be drained after an early match (the entry peek in scan_kernel), and the
+// cross-lane kernels (pairs >= 16 apart) lose 5 % with it: each wave re-loads its halo chunks per tile.
+int launch_grid(int dev, int mode, uint64_t ntiles, uint64_t *tpb, uint64_t *blocks)
+{
+    if (*tpb == 0) {
+        DeviceInfo di;
+        if (int rc = device_info(dev, &di)) return rc;
+        *tpb = ntiles / ((uint64_t)di.cus * (mode == 0 ? 256 : 128));
+        if (*tpb > (uint64_t)kAutoTilesPerBlock) *tpb = kAutoTilesPerBlock;
+        if (*tpb < 1) *tpb = 1;
+    }
+    *blocks = (ntiles + *tpb - 1) / *tpb;
+    while (*blocks > 0x7fffffffull) {        // gridDim.x limit
+        *tpb *= 2;
+        *blocks = (ntiles + *tpb - 1) / *tpb;
+    }
+    if (*blocks < 1) *blocks = 1;
+    return SS_OK;
+}
+
 namespace {
 
 // ---- kernel selection -------------------------------------------------------------------------------
@@ -108,20 +160,6 @@ struct Launch {
 
 // (Workgroups per CU, the pair-alone kernels and the filter bytes of `new`-built searchers on large haystacks: ss_census.hip.)
 constexpr int kAutoU = 4;
-constexpr int kAutoTilesPerBlock = 2;    // 32 KiB contiguous per workgroup at U = 4 (profiles/r01/tiles_per_block_sweep.jsonl)
-
-// Unused dynamic LDS that leaves room for exactly `occ` workgroups of `block` threads per CU (160 KiB of LDS).
-uint32_t occupancy_pad(int occ, unsigned block)
-{
-    const uint32_t per = (160u * 1024u) / (uint32_t)occ;
-    const uint32_t fixed = (block / ss::kWave) * ss::kNeedleLds;
-    // (1 KiB short of the share: the kernels also own a few bytes of static LDS - the completion word's workgroup flag -
-    // and a workgroup's allocation is rounded up to the hardware's granule)
-    uint32_t pad = per > fixed + 2048 ? ((per - fixed - 1024) & ~1023u) : 0;
-    if (pad > 64u * 1024u - fixed) pad = 64u * 1024u - fixed;
-    return pad;
-}
-
 // Workgroups per CU.  Since the cold half of the Problem left the registers (scan_kernels.hpp, ColdInKernarg) the multi-byte
 // kernels need 77-83 VGPRs, so the register file would admit six workgroups of four waves per CU; how many actually run is
 // set per launch through unused dynamic LDS.  Measured in one process on one buffer (tools/occ_probe.py,
@@ -293,14 +331,12 @@ int enqueue_scan(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t 
     pr.host_flag = host_flag;
     pr.epoch = epoch;
     const bool one_byte = ps.one_byte;
-    const size_t fa = ps.fa, position = ps.position, position3 = ps.position3;
+    const size_t fa = ps.fa, position = ps.position;
     const uint32_t sh = (uint32_t)(position % 16);
 
-    // Workgroups per CU.  Without census counts: a guess from the NEEDLE (every filter byte text-like -> the haystack is
-    // presumably text; single-stream kernels only) - or four, when the filter bytes have just been chosen for being rare HERE.
-    const bool text_like = !one_byte && ss::byte_rarity_rank(s->needle[fa]) >= 64 && ss::byte_rarity_rank(s->needle[fa + position]) >= 64 &&
-                           ss::byte_rarity_rank(s->needle[fa + position3]) >= 64;
-    int occ = !one_byte && text_like && pr.d == 0 && !hints.have_triple ? 6 : 4;      // (autotune off: this guess is all there is)
+    // Workgroups per CU.  Without census counts: a guess from the NEEDLE - or four, when the filter bytes have just been chosen for
+    // being rare HERE.
+    int occ = hints.have_triple ? 4 : guess_workgroups_per_cu(s, pr, ps);             // (autotune off: this guess is all there is)
     bool pair_alone = false;
     if (hints.have_counts) {
         occ = hints.workgroups_per_cu;
@@ -320,32 +356,14 @@ int enqueue_scan(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t 
         if (blocks > ntiles) blocks = ntiles;
         tpb = 0;
     } else {
-        if (s->grid < 0) {
-            tpb = (uint64_t)(-(int64_t)s->grid);
-        } else {
-            // Short-lived workgroups: two tiles (32 KiB) each from 2 GiB up (from 1 GiB for filter pairs >= 16 apart), one
-            // below.  The hardware dispatcher hands out tiles in address order, so the set of lines in flight
-            // stays one narrow, advancing window, and a fresh workgroup issues its loads the moment a slot
-            // frees up.  Measured (profiles/r01/tiles_per_block_sweep.jsonl, tiles_1_vs_2.txt; 16-byte needle):
-            // 64 GiB 7.40-7.43 TB/s at 2 tiles per workgroup vs 7.28 at 4, 7.21 at 8, 7.11 at 64.  One tile is
-            // +2 % at 1 GiB, within +-0.7 % from 4 GiB up (and +1.5 % for one-byte needles), but twice as many
-            // workgroups have to be drained after an early match (the entry peek in scan_kernel), and the
-            // cross-lane kernels (pairs >= 16 apart) lose 5 % with it: each wave re-loads its halo chunks per tile.
-            DeviceInfo di;
-            if (int rc = device_info(pd->dev, &di)) return rc;
-            tpb = ntiles / ((uint64_t)di.cus * (l.mode == 0 ? 256 : 128));
-            if (tpb > (uint64_t)kAutoTilesPerBlock) tpb = kAutoTilesPerBlock;
-            if (tpb < 1) tpb = 1;
-            // ... unless the census has counted candidates (ss_census.hip: two tiles at four workgroups per CU where candidate tiles are
-            // no rarity, one at five and six whatever the size; single-stream kernels, launches that follow the census's shape)
-            if (l.mode == 0 && s->variant == 0 && hints.have_counts && hints.tiles_per_workgroup != 0 && occ == hints.workgroups_per_cu)
-                tpb = (uint64_t)hints.tiles_per_workgroup;
-        }
-        blocks = (ntiles + tpb - 1) / tpb;
-        while (blocks > 0x7fffffffull) {        // gridDim.x limit
-            tpb *= 2;
-            blocks = (ntiles + tpb - 1) / tpb;
-        }
+        // a tuning grid's tiles per workgroup; what the census says when it has counted candidates (ss_census.hip: two tiles at four
+        // workgroups per CU where candidate tiles are no rarity, one at five and six whatever the size; single-stream kernels,
+        // launches that follow the census's shape); else launch_grid's own choice
+        tpb = 0;
+        if (s->grid < 0) tpb = (uint64_t)(-(int64_t)s->grid);
+        else if (l.mode == 0 && s->variant == 0 && hints.have_counts && hints.tiles_per_workgroup != 0 && occ == hints.workgroups_per_cu)
+            tpb = (uint64_t)hints.tiles_per_workgroup;
+        if (int rc = launch_grid(pd->dev, l.mode, ntiles, &tpb, &blocks)) return rc;
     }
     if (blocks < 1) blocks = 1;
     __atomic_store_n(&pd->last_occ, s->variant == 0 ? occ : 0, __ATOMIC_RELAXED);
