@@ -729,6 +729,29 @@ __device__ __forceinline__ uint32_t exact_verify_piece_all(const u32x4 &A, const
     return mask;
 }
 
+// sum of v over the wave, in every lane: DPP within rows of 16, then the four rows' sums
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xf, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140 /* row_mirror */, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
+           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+
+// sum of v over the lanes below this one (emit launches only: tiles that hold matches)
+__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t v, int lane)
+{
+    uint32_t x = v;
+#pragma unroll
+    for (int k = 1; k < kWave; k <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)x, (unsigned)k, kWave);
+        if (lane >= k) x += y;
+    }
+    return x - v;
+}
+
 // tells the compiler that a 64-bit value is wave-uniform (SGPR pair)
 __device__ __forceinline__ uint64_t uniform64(uint64_t x)
 {

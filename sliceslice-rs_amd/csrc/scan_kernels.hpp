@@ -45,6 +45,7 @@
 // (or uint64 minimum), read with relaxed agent-scope loads and scalar-cache peeks.
 #pragma once
 #include "scan_filters.hpp"
+#include "lines_tiles.hpp"
 
 namespace ss {
 
@@ -92,36 +93,14 @@ struct AllTiles {
     uint32_t *s_wave;         // LDS: one count per wave of the workgroup
 };
 
-// sum of v over the wave, in every lane: DPP within rows of 16, then the four rows' sums
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141 /* row_half_mirror */, 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140 /* row_mirror */, 0xf, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
-           (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-}
-
-// sum of v over the lanes below this one (emit launches only: tiles that hold matches)
-__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t v, int lane)
-{
-    uint32_t x = v;
-#pragma unroll
-    for (int k = 1; k < kWave; k <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)x, (unsigned)k, kWave);
-        if (lane >= k) x += y;
-    }
-    return x - v;
-}
-
 template <int Q, int MODE, bool ONE_BYTE, int U, int NTMODE, bool FIND = false, bool L8 = false, bool LAZY_ORDER = false,
-          typename ColdT = ColdInRegisters, bool ALL = false>
+          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false>
 __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_t *s_needle_block, uint64_t tile0,
                                            uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr)
 {
     static_assert(!L8 || (MODE == 0 && !FIND), "the 8-byte layout covers the single-stream bool kernels");
     static_assert(!ALL || (!FIND && !L8 && !LAZY_ORDER), "the all-matches mode has kernels of its own (scan_all_kernel)");
+    static_assert(!LINES || ALL, "the matching-lines mode (lines_scan_kernel, lines_tiles.hpp) is built on the all-matches one");
     static_assert(Q != kQDynamic || (MODE == 0 && !L8), "a run-time window is for the single-stream kernels' three-byte phase");
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "single-stream kernels only");
     constexpr bool SHIFTED = MODE >= 2;
@@ -162,10 +141,16 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     bool dense = false;                                                     // L8: the previous tile had candidates
     const int d = (int)pr.d;                                                // SHIFTED: 1 <= d <= 62
     // ALL: the match masks of the wave's pieces in the current tile (emit launches), and what happens at the end of every tile
+    // LINES (lines_scan_kernel only): `sink` is the launch's LineTiles instead; the match masks are kept for every tile, next to the
+    // delimiter masks of the same registers, and the end of a tile is line_tile_done's.
     AllTiles *all = static_cast<AllTiles *>(sink);
+    LineTiles *lines = static_cast<LineTiles *>(sink);
     uint32_t all_mask[U];
+    uint32_t line_dm[U];
     auto tile_done = [&](uint64_t tile) {
-        if constexpr (ALL) {
+        if constexpr (LINES) {
+            line_tile_done<U>(*lines, line_dm, all_mask, tile, (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64, lane, wave, wpb);
+        } else if constexpr (ALL) {
             if (all->emit) {
                 uint32_t c = 0;
 #pragma unroll
@@ -206,7 +191,10 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     };
 
     for (uint64_t tile = tile0; tile < tile_end; tile_done(tile), tile += tile_step) {
-        if constexpr (ALL) {
+        if constexpr (LINES) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) all_mask[u] = 0;
+        } else if constexpr (ALL) {
             if (all->emit) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) all_mask[u] = 0;
@@ -422,6 +410,8 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
         if (have16) run_phase1(std::true_type{}, std::true_type{});
         else if (full) run_phase1(std::false_type{}, std::true_type{});
         else run_phase1(std::false_type{}, std::false_type{});
+        // (the delimiters are taken from every tile, candidates or not)
+        if constexpr (LINES) line_capture<U>(A, chunk0, lane, *lines, line_dm);
         if (FIND) {
             const uint64_t first = chunk0 * 16 > pr.mis ? chunk0 * 16 - pr.mis : 0;   // lowest index this wave can report
             if (best_now <= pr.find_base + first) {                                     // all of it lies right of a match
@@ -606,8 +596,12 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                         const uint64_t far_off = MODE == 0 && !ONE_BYTE ? uniform64(cold()->far_off) : 0;
                         mk = verify_flags_all<ONE_BYTE>(g, chunk0 + 64 * u + lane, pr, va, s_needle, far_off);
                     }
-                    if (all->emit) all_mask[u] = mk;
-                    else all->lane_count += (uint32_t)__builtin_popcount(mk);
+                    if constexpr (LINES) {
+                        all_mask[u] = mk;
+                    } else {
+                        if (all->emit) all_mask[u] = mk;
+                        else all->lane_count += (uint32_t)__builtin_popcount(mk);
+                    }
                     continue;
                 }
                 uint64_t where = 0;

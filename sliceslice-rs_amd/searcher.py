@@ -109,6 +109,13 @@ MATCHES_BATCHED_ABI = {
     "ss_count_batched": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "ss_find_all_batched": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_lines.h: the lines that contain a needle (count, records) - libsliceslice_hip_lines.so only (the matches
+# library's objects plus the matching-lines scan)
+LINES_ABI = {
+    "ss_count_lines_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64]),
+    "ss_count_lines_device_async": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
+    "ss_find_lines_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -207,11 +214,13 @@ def _load(path):
     _bind(L, SERVICE_ABI, strict=False)
     _bind(L, MATCHES_ABI, strict=False)
     _bind(L, MATCHES_BATCHED_ABI, strict=False)
+    _bind(L, LINES_ABI, strict=False)
     _bind(L, HOOKS_ABI, strict=False)
     L.has_hooks = hasattr(L, "ss_debug_fail_next_scans")
     L.has_service = hasattr(L, "ss_service_start")
     L.has_matches = hasattr(L, "ss_count_device")
     L.has_matches_batched = hasattr(L, "ss_count_batched")
+    L.has_lines = hasattr(L, "ss_count_lines_device")
     return L
 
 
@@ -229,6 +238,7 @@ _tuning = None
 _service = None
 _matches = None
 _matches_batched = None
+_lines = None
 
 
 def tools_lib():
@@ -312,6 +322,41 @@ class matches_batched_build:
         global _lib
         _lib = self._saved
         return False
+
+
+class lines_build:
+    """``with ss.lines_build():`` - inside the block ``lib()`` is libsliceslice_hip_lines.so: every function of the matches library
+    (so ``count`` / ``find_all`` of searchers created inside work too) plus the matching-lines scan
+    (include/sliceslice_hip_lines.h: ``count_lines`` / ``find_lines``).  Searchers belong to the library that made them, so the
+    searchers whose ``count_lines`` / ``find_lines`` are called must be created inside the block; they keep working after it."""
+
+    def __enter__(self):
+        global _lib, _lines
+        if _lines is None:
+            _lines = _load(_build.build_lines())
+        self._saved, _lib = _lib, _lines
+        return _lines
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = self._saved
+        return False
+
+
+def _lines_lib(L):
+    if not getattr(L, "has_lines", False):
+        raise SlicesliceError(SS_ERR_ARGUMENT, "count_lines / find_lines are not part of this library: they live in "
+                                               "libsliceslice_hip_lines.so - create the searcher inside `with ss.lines_build():`")
+    return L
+
+
+def _delimiter_byte(delimiter):
+    """The one delimiter byte of count_lines / find_lines: an int 0..255 or a bytes object of length one."""
+    if isinstance(delimiter, (bytes, bytearray)):
+        if len(delimiter) != 1:
+            raise ValueError("the line delimiter is ONE byte, got %d" % len(delimiter))
+        return delimiter[0]
+    return int(delimiter)
 
 
 def _matches_batched_lib():
@@ -546,6 +591,61 @@ class DynamicHipSearcher:
                                           d_offsets.numel(), ctypes.byref(total)))
         return total.value
 
+    # -- the lines that contain the needle (libsliceslice_hip_lines.so: searchers made inside `with ss.lines_build():`) ------
+    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+        """int: the number of lines of ``haystack`` (cut at every ``delimiter`` byte) that hold at least one occurrence of the
+        needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines."""
+        L = _lines_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_count_lines_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
+        return c.value
+
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None):
+        """Enqueue only (ss_count_lines_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
+        L = _lines_lib(self._L)
+        with _on_device_of(haystack):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_count_lines_device_async(self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st,
+                                                   d_count.data_ptr()))
+
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number): three int64 tensors on the haystack's device, one entry per matching line in ascending order - the
+        offset of its first byte, the offset of the delimiter that closes it (len for a last line without one) and its 1-based
+        line number (ss_find_lines_device).  capacity=None: counted first (ss_count_lines_device: one more pass over the haystack, as
+        ``find_all`` does), then exactly that many; with a capacity the haystack is read at most twice and the leftmost ``capacity``
+        records come back."""
+        import torch
+        L = _lines_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        d = _delimiter_byte(delimiter)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            if capacity is None:
+                self._ck(L.ss_count_lines_device(self._h, ptr, length, d, st, ctypes.byref(total)))
+                capacity = total.value
+            out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+            p = [out[k].data_ptr() if capacity else None for k in range(3)]
+            self._ck(L.ss_find_lines_device(self._h, ptr, length, d, st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
+        k = min(int(capacity), total.value)
+        return out[0, :k], out[1, :k], out[2, :k]
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+        """ss_find_lines_device into the caller's 8-byte device tensors (each may be None: not wanted); returns the total count."""
+        L = _lines_lib(self._L)
+        ptr, length, t = self._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+            self._ck(L.ss_find_lines_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
+                                            ctypes.byref(total)))
+        return total.value
+
     # -- tuning / measurement hooks ------------------------------------------------------------------
     @property
     def filter(self):
@@ -670,6 +770,18 @@ class MemchrHipSearcher:
 
     def find_all(self, haystack, capacity=None, stream=None):
         return self._inner.find_all(haystack, capacity, stream)
+
+    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+        return self._inner.count_lines(haystack, delimiter, stream)
+
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None):
+        return self._inner.count_lines_async(haystack, d_count, delimiter, stream)
+
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        return self._inner.find_lines(haystack, delimiter, capacity, stream)
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+        return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream)
 
 
 def shard_range(length, needle_len, nranks, rank):

@@ -1,0 +1,163 @@
+"""CPU checks of the matching-lines calls (include/sliceslice_hip_lines.h): the header, the ctypes table and the Rust module agree
+symbol by symbol; libsliceslice_hip_lines.so exports exactly the three headers while the other libraries export what they did; the
+lines kernels meet the scan kernels' bar; the Python methods refuse outside lines_build(); the rule restated here reproduces
+tests/golden/lines_kat.json."""
+import ctypes
+import hashlib
+import json
+import os
+import re
+import struct
+import subprocess
+import sys
+
+import pytest
+
+import sliceslice_rs_amd as ss
+from test_bindings_cpu import header_prototypes, rust_prototypes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+LINES = ["ss_count_lines_device", "ss_count_lines_device_async", "ss_find_lines_device"]
+
+
+def _build():
+    return sys.modules["sliceslice_rs_amd._build"]
+
+
+def _exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
+
+
+def lines_rule(data, needle, delimiter):
+    """[(begin, end, number)]: the view cut at every delimiter, a trailing empty piece dropped, lines that contain the needle."""
+    pieces = data.split(bytes([delimiter]))
+    if pieces[-1] == b"":
+        pieces.pop()
+    out, begin = [], 0
+    for k, piece in enumerate(pieces):
+        if needle in piece:
+            out.append((begin, begin + len(piece), k + 1))
+        begin += len(piece) + 1
+    return out
+
+
+def test_header_ctypes_and_rust_agree():
+    c = header_prototypes("sliceslice_hip_lines.h")
+    assert sorted(c) == sorted(ss.searcher.LINES_ABI) == LINES
+    assert c["ss_count_lines_device"] == ("i32", ["ptr", "ptr", "usize", "i32", "ptr", "ptr"])
+    assert c["ss_count_lines_device_async"] == ("i32", ["ptr", "ptr", "usize", "i32", "ptr", "ptr"])
+    assert c["ss_find_lines_device"] == ("i32", ["ptr", "ptr", "usize", "i32", "ptr", "ptr", "ptr", "ptr", "u64", "ptr"])
+    r = rust_prototypes("hip_lines.rs")
+    assert r == c, (r, c)
+    norm = lambda t: "ptr" if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))) else \
+        {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]           # noqa: E731
+    for name, (res, args) in ss.searcher.LINES_ABI.items():
+        got = (norm(res), [norm(a) for a in args])
+        want = c[name]
+        assert [a.replace("usize", "u64") for a in got[1]] == [a.replace("usize", "u64") for a in want[1]] and got[0] == want[0], name
+    # none of it is in the other headers
+    for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h"):
+        assert not set(c) & set(header_prototypes(h)), h
+    assert '#include "sliceslice_hip_matches.h"' in open(os.path.join(ROOT, "include", "sliceslice_hip_lines.h")).read()
+
+
+def test_the_lines_library_exports_three_headers_and_the_others_what_they_did():
+    b = _build()
+    product = list(header_prototypes())
+    matches = list(header_prototypes("sliceslice_hip_matches.h"))
+    batched = list(header_prototypes("sliceslice_hip_matches_batched.h"))
+    assert _exported(b.build_lines()) == sorted(product + matches + LINES)
+    assert _exported(ss.build()) == sorted(product)
+    assert _exported(b.build_matches()) == sorted(product + matches)
+    assert _exported(b.build_matches_batched()) == sorted(product + matches + batched)
+    assert os.path.basename(b.lines_library_path()) == "libsliceslice_hip_lines.so"
+
+
+def test_the_lines_kernels_meet_the_scan_kernels_bar():
+    rows = _build().lines_kernel_resources()
+    assert len([r for r in rows if re.match(r"void ss::scan_kernel<", r["name"])]) == 22         # the product's objects, unchanged
+    assert len([r for r in rows if re.match(r"void ss::scan_all_kernel<", r["name"])]) == 9      # ... and the matches library's
+    scans, others = {}, {}
+    for r in rows:
+        if "lines_" not in r["name"]:
+            continue
+        # the bar of every kernel of the scan family: no scratch memory, no spilled vector registers, four waves per SIMD
+        assert r["scratch_bytes_per_lane"] == 0 and r["vgpr_spills"] == 0, r
+        assert r["waves_per_simd"] >= 4 and r["vgprs"] <= 128, r
+        m = re.match(r"void ss::lines_scan_kernel<(\d), (\d), (true|false)>", r["name"])
+        if m:
+            scans[m.groups()] = r
+            assert r.get("lds_bytes", 0) <= 1024, r
+        else:
+            others[re.sub(r"[<(].*", "", r["name"].replace("void ", ""))] = r
+    # one scan kernel per (Q, MODE, one-byte) combination find_all() has: 4 Q x MODE 0, 4 Q x MODE 2, one-byte
+    assert sorted(scans) == sorted([(str(q), m, "false") for q in range(4) for m in ("0", "2")] + [("0", "0", "true")])
+    assert sorted(others) == ["ss::lines_chunk_kernel", "ss::lines_combine_kernel", "ss::lines_plain_kernel"], sorted(others)
+    product = json.load(open(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", "kernel_resources.json")))
+    assert len(product) == 37
+    # the lines kernels are in no other library's record
+    for other in (_build().matches_kernel_resources(), _build().matches_batched_kernel_resources(), product):
+        assert not [r for r in other if "lines_" in r["name"]]
+
+
+def test_methods_refuse_outside_the_lines_library():
+    class Fake:
+        _L = ss.lib()
+        _h = None
+    for meth, args in (("count_lines", (b"abc",)), ("find_lines", (b"abc",)), ("count_lines_async", (None, None)),
+                       ("find_lines_into", (b"abc", None, None, None, 0))):
+        with pytest.raises(ss.SlicesliceError, match="lines_build"):
+            getattr(ss.DynamicHipSearcher, meth)(Fake(), *args)
+    with ss.matches_build():
+        Fake._L = ss.lib()
+    with pytest.raises(ss.SlicesliceError, match="lines_build"):
+        ss.DynamicHipSearcher.count_lines(Fake(), b"abc")
+    assert all(hasattr(ss.MemchrHipSearcher, m) for m in ("count_lines", "count_lines_async", "find_lines", "find_lines_into"))
+
+
+def test_the_delimiter_is_one_byte():
+    d = ss.searcher._delimiter_byte
+    assert d(b"\n") == 10 and d(b"\x00") == 0 and d(255) == 255 and d(bytearray(b"\xff")) == 255
+    for bad in (b"", b"\r\n"):
+        with pytest.raises(ValueError):
+            d(bad)
+
+
+def test_the_rule_reproduces_the_fixture():
+    kat = json.load(open(os.path.join(GOLDEN, "lines_kat.json")))
+    data = open(os.path.join(GOLDEN, "data", "i386.txt"), "rb").read()
+    words = open(os.path.join(GOLDEN, "data", "words.txt"), "rb").read().split()
+    assert kat["i386_lines"] == len(lines_rule(data, b"", 10)) == 20854
+    assert len(words) == kat["words"] == len(kat["count_lines"]) == 4585
+    assert sum(kat["count_lines"]) == kat["total"] == 410509
+    lines = data.split(b"\n")[:-1]
+    for k in list(range(0, len(words), 97)) + [words.index(b"the"), words.index(b"e")]:
+        assert sum(1 for l in lines if words[k] in l) == kat["count_lines"][k], words[k]
+    assert kat["count_lines"][words.index(b"the")] == 4801 and kat["count_lines"][words.index(b"e")] == 11596
+    assert len(kat["records"]) >= 50
+    for w, want in kat["records"].items():
+        r = lines_rule(data, w.encode("latin-1"), 10)
+        assert len(r) == want["lines"], w
+        assert hashlib.sha256(b"".join(struct.pack("<3Q", *t) for t in r)).hexdigest() == want["sha256"], w
+    whats = " ".join(c["what"] for c in kat["cases"])
+    for topic in ("empty haystack", "only delimiters", "no trailing delimiter", "empty needle", "equal to the delimiter", "0x00", "0xFF"):
+        assert topic in whats, topic
+    for c in kat["cases"]:
+        got = lines_rule(bytes.fromhex(c["haystack"]), bytes.fromhex(c["needle"]), c["delimiter"])
+        assert got == [tuple(r) for r in c["records"]], c["what"]
+
+
+def test_tools_and_documents_know_the_lines_calls():
+    grep = open(os.path.join(ROOT, "tools", "grep_hip.py")).read()
+    assert "--count-lines" in grep and "--lines" in grep and "--count" in grep and "--offsets" in grep
+    for rel in ("tools/fuzz_lines.py", "tools/lines_bench.py", "tests/golden/make_lines_golden.py",
+                "sliceslice-rs_amd/bindings/rust/hip_lines.rs", "include/sliceslice_hip_lines.h"):
+        assert os.path.exists(os.path.join(ROOT, rel)), rel
+    # the occurrence count is no longer called grep -c
+    for rel in ("include/sliceslice_hip_matches.h", "README.md", "tools/grep_hip.py"):
+        text = open(os.path.join(ROOT, rel)).read()
+        for line in text.splitlines():
+            if "grep -c" in line and "occurrence" in line.lower():
+                assert "not" in line.lower() or "lines" in line.lower(), (rel, line)

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""./grep_hip.py <needle> <file> [--count | --offsets] - the reference's examples/grep.rs:42-56 with the "hip"
-backend: map the file, build one searcher, one search_in, print the boolean.
-  --count    grep -c style: the number of (overlapping) occurrences (libsliceslice_hip_matches.so, ss_count_device)
-  --offsets  grep -b -o style: one byte offset per line, ascending (ss_find_all_device)
+"""./grep_hip.py <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
+"hip" backend: map the file, build one searcher, one search_in, print the boolean.
+  --count        the number of (overlapping) OCCURRENCES, not lines (libsliceslice_hip_matches.so, ss_count_device)
+  --offsets      grep -b -o style: one byte offset per occurrence, ascending (ss_find_all_device)
+  --count-lines  grep -c: the number of LINES that contain the needle (libsliceslice_hip_lines.so, ss_count_lines_device)
+  --lines        grep -n: `number:line` for every line that contains the needle (ss_find_lines_device; only the records and the
+                 bytes of those lines travel to the host)
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
 per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched)."""
 import os
@@ -27,6 +30,25 @@ def count_patterns(patterns, filename):
         return counts.cpu().tolist()
 
 
+def matching_lines(searcher, data):
+    """[(number, line bytes)] of the lines that contain the needle: the records, then only those byte ranges, come to the host."""
+    import torch
+    hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+    begin, end, number = searcher.find_lines(hay)
+    if begin.numel() == 0:
+        return []
+    # gather the matching lines' bytes on the device: one copy of sum(end - begin) bytes instead of the whole file
+    length = end - begin
+    start = torch.cumsum(length, 0) - length
+    idx = torch.repeat_interleave(begin - start, length) + torch.arange(int(length.sum()), device=hay.device)
+    packed = hay[idx].cpu().numpy().tobytes()
+    out, at = [], 0
+    for n, ln in zip(number.cpu().tolist(), length.cpu().tolist()):
+        out.append((n, packed[at:at + ln]))
+        at += ln
+    return out
+
+
 def main():
     argv, patterns = [], []
     it = iter(sys.argv[1:])
@@ -44,9 +66,19 @@ def main():
             raise SystemExit("./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file>")
         sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
         return
-    if len(args) < 2 or flags - {"--count", "--offsets", "--rare-position"}:
-        raise SystemExit("./grep_hip.py <needle> <file> [--count | --offsets]")
+    if len(args) < 2 or flags - {"--count", "--offsets", "--count-lines", "--lines", "--rare-position"}:
+        raise SystemExit("./grep_hip.py <needle> <file> [--count | --offsets | --count-lines | --lines]")
     needle, filename = args[0].encode(), args[1]
+    if "--count-lines" in flags or "--lines" in flags:
+        with ss.lines_build():
+            searcher = ss.DynamicHipSearcher.new(needle)
+        data = open(filename, "rb").read()
+        if "--lines" in flags:
+            for n, line in matching_lines(searcher, data):
+                sys.stdout.buffer.write(b"%d:%s\n" % (n, line))
+        else:
+            print(searcher.count_lines(data))
+        return
     if "--count" in flags or "--offsets" in flags:
         with ss.matches_build():
             searcher = ss.DynamicHipSearcher.new(needle)
