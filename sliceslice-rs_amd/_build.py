@@ -9,6 +9,8 @@
                                   (include/sliceslice_hip_matches_batched.h: count and find-all for a batch of problems): opt-in too
     libsliceslice_hip_lines.so    the matches library's objects plus the matching-lines scan (include/sliceslice_hip_lines.h: count
                                   and list the lines that contain a needle): opt-in too
+    libsliceslice_hip_nocase.so   the lines library's objects plus the case-folding scans (include/sliceslice_hip_nocase.h: count,
+                                  find-all and the matching lines ignoring ASCII case): opt-in too
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
     libsliceslice_hip_tuning.so   the product's sources with -DSS_TUNING_VARIANTS -DSS_TEST_HOOKS: every kernel variant,
                                   ss_searcher_set_variant / _set_grid, fault injection (tools/, the variant and hook tests)
@@ -37,12 +39,14 @@ _SERVICE_SO = os.path.join(_CSRC, "libsliceslice_hip_service.so")
 _MATCHES_SO = os.path.join(_CSRC, "libsliceslice_hip_matches.so")
 _MATCHES_BATCHED_SO = os.path.join(_CSRC, "libsliceslice_hip_matches_batched.so")
 _LINES_SO = os.path.join(_CSRC, "libsliceslice_hip_lines.so")
+_NOCASE_SO = os.path.join(_CSRC, "libsliceslice_hip_nocase.so")
 # host-side translation units (ss_internal.hpp lists what each holds) ...
 _HOST_SOURCES = ["ss_core.hip", "ss_scan.hip", "ss_census.hip", "ss_host.hip", "ss_batched.hip", "ss_comm.hip"]
 _SERVICE_SOURCES = ["ss_service.hip"]       # NOT in the product: libsliceslice_hip_service.so and the hooks builds
 _MATCHES_SOURCES = ["ss_matches.hip", "scan_inst_all.hip"]     # NOT in the product: libsliceslice_hip_matches.so and ..._matches_batched.so
 _MATCHES_BATCHED_SOURCES = ["ss_matches_batched.hip", "scan_inst_all_batched.hip"]     # libsliceslice_hip_matches_batched.so only
-_LINES_SOURCES = ["ss_lines.hip", "scan_inst_lines.hip"]       # libsliceslice_hip_lines.so only
+_LINES_SOURCES = ["ss_lines.hip", "scan_inst_lines.hip"]       # libsliceslice_hip_lines.so and ..._nocase.so
+_NOCASE_SOURCES = ["ss_nocase.hip", "scan_inst_nocase.hip"]    # libsliceslice_hip_nocase.so only
 # ... and the scan kernel family, one explicit-instantiation unit per (U, load flavour, search / find).  The product holds what
 # the constructors and ss_searcher_set_filter3 can select (scan_launch.hpp::kernel_built): U = 4, non-temporal loads.
 _KERNEL_SOURCES = ["scan_inst_u4_nt1.hip", "scan_inst_find_nt1.hip"]
@@ -50,10 +54,12 @@ _SOURCES = _HOST_SOURCES + _KERNEL_SOURCES
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
 _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
-            "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "lines_scan_body.hpp", "lines_host.hpp", "matches_host.hpp",
+            "nocase_kernels.hpp", "nocase_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_lines.h"),
+            os.path.join("..", "..", "include", "sliceslice_hip_nocase.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_service.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_tuning.h")]
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden"]
@@ -102,6 +108,14 @@ def lines_library_path():
 
 def lines_resources_path():
     return _LINES_RESOURCES
+
+
+def nocase_library_path():
+    return _NOCASE_SO
+
+
+def nocase_resources_path():
+    return _NOCASE_RESOURCES
 
 
 def native_bench_path():
@@ -206,6 +220,7 @@ _RESOURCES = os.path.join(_CSRC, "kernel_resources.json")
 _MATCHES_RESOURCES = os.path.join(_CSRC, "kernel_resources_matches.json")
 _MATCHES_BATCHED_RESOURCES = os.path.join(_CSRC, "kernel_resources_matches_batched.json")
 _LINES_RESOURCES = os.path.join(_CSRC, "kernel_resources_lines.json")
+_NOCASE_RESOURCES = os.path.join(_CSRC, "kernel_resources_nocase.json")
 _RES_KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
              "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills",
              "LDS Size [bytes/block]": "lds_bytes"}
@@ -305,6 +320,23 @@ def lines_kernel_resources():
     matching-lines ones."""
     build_lines()
     return json.load(open(_LINES_RESOURCES))
+
+
+def build_nocase(force=False, verbose=False):
+    """The lines library's objects + the case-folding scans (csrc/ss_nocase.hip, scan_inst_nocase.hip) ->
+    csrc/libsliceslice_hip_nocase.so (include/sliceslice_hip_nocase.h).  The library's kernels are recorded in
+    csrc/kernel_resources_nocase.json."""
+    build_lines(verbose=verbose)                            # the product's, the matches and the lines library's objects are shared
+    with _Lock(".build_nocase.lock"):
+        return _build_variant(_NOCASE_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES + _LINES_SOURCES + _NOCASE_SOURCES,
+                              own=_NOCASE_SOURCES, record_resources=True, resources=_NOCASE_RESOURCES)
+
+
+def nocase_kernel_resources():
+    """Rows of csrc/kernel_resources_nocase.json (written by build_nocase()): the product's kernels, the all-matches ones, the
+    matching-lines ones and the case-folding ones."""
+    build_nocase()
+    return json.load(open(_NOCASE_RESOURCES))
 
 
 def build_tools(force=False, verbose=False):

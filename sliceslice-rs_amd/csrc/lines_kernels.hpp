@@ -17,93 +17,14 @@
 // atomic anywhere.
 #pragma once
 #include "lines_launch.hpp"
+#include "lines_scan_body.hpp"
 
 namespace ss {
 
 
 // Contiguous tiles per workgroup (1 <= tiles_per_block <= kLineTilesPerBlock), so that workgroup order is address order.
-template <int Q, int MODE, bool ONE_BYTE>
-__global__ void __launch_bounds__(kMaxBlock) lines_scan_kernel(const Problem pr, LineArgs la, uint64_t tiles_per_block)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t s_needle[];
-    __shared__ uint64_t s_last[kLineTilesPerBlock * kMaxWavesPerBlock];
-    __shared__ uint32_t s_flags[kLineTilesPerBlock * kMaxWavesPerBlock];
-    __shared__ uint32_t s_nd[kMaxWavesPerBlock], s_cl[kMaxWavesPerBlock];
-    constexpr int U = 4;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int wpb = (int)(blockDim.x / kWave);
-    const unsigned tile_shift = (unsigned)__builtin_ctz(blockDim.x / kWave) + (unsigned)__builtin_ctz(U);
-    const uint64_t ntiles = (pr.npieces + ((uint64_t)1 << tile_shift) - 1) >> tile_shift;
-    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_block;
-    const uint64_t t1 = t0 + tiles_per_block < ntiles ? t0 + tiles_per_block : ntiles;
-    LineTiles lt;
-    lt.delim_x4 = la.delim * 0x01010101u;
-    lt.dlo = la.dlo;
-    lt.dhi = la.dhi;
-    lt.hshift = la.hshift;
-    lt.emit = la.mode == kLinesEmit;
-    lt.tile0 = t0;
-    lt.lane_ndelim = lt.lane_closed = 0;
-    lt.s_last = s_last;
-    lt.s_flags = s_flags;
-    lt.s_nd = s_nd;
-    lt.s_cl = s_cl;
-    lt.at = LinePre{0, 0, 0, 0, 0};
-    lt.begin = la.begin;
-    lt.end = la.end;
-    lt.number = la.number;
-    lt.capacity = la.capacity;
-    if (la.mode == kLinesEmit) {
-        const LinePre *p = la.pre + la.part0 + blockIdx.x;
-        lt.at.ndelim = uniform64(p->ndelim);
-        lt.at.rank = uniform64(p->rank);
-        lt.at.last = uniform64(p->last);
-        lt.at.carry = (uint32_t)__builtin_amdgcn_readfirstlane((int)p->carry);
-        const uint32_t closes = (uint32_t)__builtin_amdgcn_readfirstlane((int)p->closes);
-        if (closes == 0 || lt.at.rank >= la.capacity) return;
-    }
-    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, true>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &lt);
-    if (la.mode == kLinesEmit) return;
-    const uint32_t wn = wave_sum(lt.lane_ndelim), wc = wave_sum(lt.lane_closed);
-    if (lane == 0) {
-        s_nd[wave] = wn;
-        s_cl[wave] = wc;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // the wave summaries in address order: tile by tile, wave by wave
-        LineSum sum = {0, 0, 0, 0, 0};
-        for (int w = 0; w < wpb; ++w) {
-            sum.ndelim += s_nd[w];
-            sum.closed += s_cl[w];
-        }
-        uint32_t f = 0;
-        uint64_t joins = 0, firsts = 0;
-        for (uint64_t t = 0; t < t1 - t0; ++t) {
-            for (int w = 0; w < wpb; ++w) {
-                const uint32_t slot = (uint32_t)t * kMaxWavesPerBlock + (uint32_t)w;
-                const uint32_t e = s_flags[slot];
-                if ((e & kLineHas) == 0) {
-                    if (e & kLineHead) f |= (f & kLineHas) ? kLineTail : (kLineHead | kLineTail);
-                    continue;
-                }
-                // (the wave counted its first delimiter's line when its own head matched: whether that line matches is decided here)
-                if (e & kLineHead) ++firsts;
-                if (f & kLineHas) {
-                    if ((f & kLineTail) | (e & kLineHead)) ++joins;
-                    f = kLineHas | (f & kLineHead) | (e & kLineTail);
-                } else {
-                    f = kLineHas | ((f | e) & kLineHead) | (e & kLineTail);
-                }
-                sum.last = s_last[slot];
-            }
-        }
-        sum.closed = sum.closed + joins - firsts;
-        sum.flags = f;
-        la.sum[la.part0 + blockIdx.x] = sum;
-    }
-}
+// (lines_scan_body.hpp holds the text, shared with the case-folding twin of nocase_kernels.hpp)
+SS_LINES_SCAN_KERNEL(lines_scan_kernel, false)
 
 // Bytes [begin, end) of the haystack in parts of part_bytes, one workgroup each (thread t: a contiguous run of the part).  No match
 // inside (EVERY = false: only a pending match in front of a part closes a line, at the part's first delimiter) or every line

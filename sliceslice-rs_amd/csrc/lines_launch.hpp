@@ -46,6 +46,8 @@ struct CombineArgs {
 
 // The matching-lines scan of one Problem (the kernel choice of launch_scan_all).  Returns false when no kernel fits.
 bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
+// (the host side takes the scan as a value of this type: ss_lines.hip, lines_host.hpp)
+typedef bool (*ScanLinesFn)(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
 // ceil((end - begin) / part_bytes) workgroups (at least one: an empty range leaves an empty summary)
 hipError_t launch_lines_plain(const PlainArgs &pa, bool every, hipStream_t st);
 // The summaries of `n` parts in chunks of kLineChunk: csum[chunk] = the chunk's summary (spread == false), or - behind the combine

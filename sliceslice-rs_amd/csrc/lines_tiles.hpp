@@ -73,8 +73,7 @@ __device__ __forceinline__ uint64_t line_advance(LinePre &s, const LineSum &e)
     return c;
 }
 
-// bit 7 of every byte of x that is zero - exact (zero_byte_flags may also flag a 0x01 above a zero byte)
-__device__ __forceinline__ uint32_t zero_bytes_exact(uint32_t x) { return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
+// (zero_bytes_exact - bit 7 of every byte that is zero, exactly - is scan_filters.hpp's: the case fold uses it too)
 
 // The delimiters of a chunk in the TRANSPOSED layout the flag words have (verify_flags_walk): byte t of dword j at bit 8t + j.
 __device__ __forceinline__ uint32_t delimiter_bits(const u32x4 &A, uint32_t dx4)
@@ -119,12 +118,10 @@ struct LineTiles {
     uint64_t capacity;
 };
 
-// the delimiter masks of a wave's U pieces (transposed layout), bytes outside the view masked out
+// bytes outside the view are masked out of the delimiter masks of a wave's U pieces
 template <int U>
-__device__ __forceinline__ void line_capture(const u32x4 (&A)[U], uint64_t chunk0, int lane, const LineTiles &lt, uint32_t (&dm)[U])
+__device__ __forceinline__ void line_clip(uint64_t chunk0, int lane, const LineTiles &lt, uint32_t (&dm)[U])
 {
-#pragma unroll
-    for (int u = 0; u < U; ++u) dm[u] = delimiter_bits(A[u], lt.delim_x4);
     if (chunk0 * 16 < lt.dlo || (chunk0 + 64 * U) * 16 > lt.dhi) {           // wave-uniform: the view's first and last tiles
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -135,6 +132,15 @@ __device__ __forceinline__ void line_capture(const u32x4 (&A)[U], uint64_t chunk
             dm[u] &= line_transposed(v);
         }
     }
+}
+
+// the delimiter masks of a wave's U pieces (transposed layout), bytes outside the view masked out
+template <int U>
+__device__ __forceinline__ void line_capture(const u32x4 (&A)[U], uint64_t chunk0, int lane, const LineTiles &lt, uint32_t (&dm)[U])
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) dm[u] = delimiter_bits(A[u], lt.delim_x4);
+    line_clip<U>(chunk0, lane, lt, dm);
 }
 
 // a lane's match mask in address order: the offsets verified on behalf of the next lane's chunk (exact_verify_piece_all, bits

@@ -1,0 +1,12 @@
+// nocase_launch.hpp - host-side entry points of the case-folding scans (nocase_kernels.hpp; defined in scan_inst_nocase.hip, used
+// by ss_nocase.hip).  Same arguments, kernel choice and return value as launch_scan_all / launch_scan_lines.
+#pragma once
+#include "lines_launch.hpp"
+#include "matches_launch.hpp"
+
+namespace ss {
+
+bool launch_scan_all_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa);
+bool launch_scan_lines_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
+
+}  // namespace ss

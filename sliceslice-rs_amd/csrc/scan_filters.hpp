@@ -107,6 +107,8 @@ struct ColdInRegisters {      // kernels that build their Problem themselves (ba
 };
 
 __device__ __forceinline__ uint32_t zero_byte_flags(uint32_t x) { return (x - 0x01010101u) & ~x; }
+// bit 7 of every byte of x that is zero - exact (zero_byte_flags may also flag a 0x01 above a zero byte)
+__device__ __forceinline__ uint32_t zero_bytes_exact(uint32_t x) { return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; }
 
 // lane l < 63 receives cur[l+1]; lane 63 keeps `last` (DPP wave_shl:1 without bound_ctrl leaves a lane
 // that has no source lane untouched, i.e. equal to the `old` operand).
@@ -135,6 +137,42 @@ __device__ __forceinline__ u32x4 load_chunk(const uint8_t *base, uint64_t chunk)
     return *p;
 }
 
+// ASCII case folding (FOLD kernels: include/sliceslice_hip_nocase.h).  Bytes 'A'..'Z' get bit 5 set, every other byte - '@', '[',
+// everything >= 0x80 - stays what it is; four bytes per dword without a carry between them: of the low seven bits h of a byte,
+// h + 0x3f has bit 7 set iff h >= 'A', h + 0x25 iff h > 'Z', and ~x keeps bytes >= 0x80 out.  The needle of such a search holds no
+// upper-case byte, so equal-ignoring-case is plain equality on folded haystack bytes: the registers are folded once behind the loads
+// (scan_tiles) and everything downstream of them stays what it is; the places that read haystack bytes from MEMORY fold them there.
+// KEEP: the matching-lines calls never fold their delimiter - a line delimiter 'A' is no 'a', and an occurrence cannot run across
+// it.  keepx4 is that byte splatted when it is an upper-case letter (no other delimiter is touched by the fold), else 0: the bytes
+// equal to it stay as they are (a zero byte is no letter, so 0 keeps nothing).
+__device__ __forceinline__ uint32_t fold_ascii4(uint32_t x)
+{
+    const uint32_t h = x & 0x7f7f7f7fu;
+    const uint32_t m = (h + 0x3f3f3f3fu) & ~(h + 0x25252525u) & ~x & 0x80808080u;
+    return x | (m >> 2);
+}
+__device__ __forceinline__ uint32_t fold_ascii4_keep(uint32_t x, uint32_t keepx4)
+{
+    const uint32_t h = x & 0x7f7f7f7fu;
+    const uint32_t m = (h + 0x3f3f3f3fu) & ~(h + 0x25252525u) & ~x & 0x80808080u & ~zero_bytes_exact(x ^ keepx4);
+    return x | (m >> 2);
+}
+__device__ __forceinline__ void fold_ascii_chunk(u32x4 &A)
+{
+    A.x = fold_ascii4(A.x); A.y = fold_ascii4(A.y); A.z = fold_ascii4(A.z); A.w = fold_ascii4(A.w);
+}
+__device__ __forceinline__ void fold_ascii_chunk_keep(u32x4 &A, uint32_t keepx4)
+{
+    A.x = fold_ascii4_keep(A.x, keepx4); A.y = fold_ascii4_keep(A.y, keepx4);
+    A.z = fold_ascii4_keep(A.z, keepx4); A.w = fold_ascii4_keep(A.w, keepx4);
+}
+// haystack bytes read from memory by the verification (rare paths: always the KEEP form)
+template <bool FOLD> __device__ __forceinline__ uint32_t hay_u32(uint32_t x, uint32_t keepx4) { return FOLD ? fold_ascii4_keep(x, keepx4) : x; }
+template <bool FOLD> __device__ __forceinline__ uint8_t hay_u8(uint8_t b, uint32_t keepx4)
+{
+    return FOLD && (uint8_t)(b - 'A') < 26 && b != (uint8_t)keepx4 ? (uint8_t)(b | 0x20) : b;
+}
+
 // Full comparison of the needle with hay[i .. i+n), four bytes per step (unaligned global dword
 // loads are legal on gfx950; the LDS/global needle side is dword-aligned by construction).
 // Lane-private (divergent) on purpose: on random data almost every candidate dies in the first dword.
@@ -142,8 +180,9 @@ struct __attribute__((packed, aligned(1))) UnalignedU32 {
     uint32_t v;
 };
 
+template <bool FOLD = false>
 __device__ __forceinline__ bool verify_candidate(const uint8_t *hay, const uint8_t *needle, uint64_t n, const uint8_t *s_needle,
-                                                 uint64_t i)
+                                                 uint64_t i, uint32_t keepx4 = 0)
 {
     const uint8_t *h = hay + i;
     const uint64_t n_lds = n < (uint64_t)kNeedleLds ? n : (uint64_t)kNeedleLds;
@@ -151,21 +190,21 @@ __device__ __forceinline__ bool verify_candidate(const uint8_t *hay, const uint8
     // sixteen bytes per step: the four haystack dwords are loaded together (one memory round trip per 16 bytes
     // instead of one per 4 - what a true match, whose every byte has to be looked at, is bound by)
     for (; k + 16 <= n_lds; k += 16) {
-        const uint32_t a0 = reinterpret_cast<const UnalignedU32 *>(h + k)->v, a1 = reinterpret_cast<const UnalignedU32 *>(h + k + 4)->v;
-        const uint32_t a2 = reinterpret_cast<const UnalignedU32 *>(h + k + 8)->v, a3 = reinterpret_cast<const UnalignedU32 *>(h + k + 12)->v;
+        const uint32_t a0 = hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k)->v, keepx4), a1 = hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k + 4)->v, keepx4);
+        const uint32_t a2 = hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k + 8)->v, keepx4), a3 = hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k + 12)->v, keepx4);
         const u32x4 nd = *reinterpret_cast<const u32x4 *>(s_needle + k);
         if (((a0 ^ nd.x) | (a1 ^ nd.y) | (a2 ^ nd.z) | (a3 ^ nd.w)) != 0) return false;
     }
     for (; k + 4 <= n_lds; k += 4)
-        if (reinterpret_cast<const UnalignedU32 *>(h + k)->v != *reinterpret_cast<const uint32_t *>(s_needle + k))
+        if (hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k)->v, keepx4) != *reinterpret_cast<const uint32_t *>(s_needle + k))
             return false;
     for (; k < n_lds; ++k)
-        if (h[k] != s_needle[k]) return false;
+        if (hay_u8<FOLD>(h[k], keepx4) != s_needle[k]) return false;
     for (; k + 4 <= n; k += 4)   // needles longer than the LDS slice continue from the global copy
-        if (reinterpret_cast<const UnalignedU32 *>(h + k)->v != reinterpret_cast<const UnalignedU32 *>(needle + k)->v)
+        if (hay_u32<FOLD>(reinterpret_cast<const UnalignedU32 *>(h + k)->v, keepx4) != reinterpret_cast<const UnalignedU32 *>(needle + k)->v)
             return false;
     for (; k < n; ++k)
-        if (h[k] != needle[k]) return false;
+        if (hay_u8<FOLD>(h[k], keepx4) != needle[k]) return false;
     return true;
 }
 
@@ -175,24 +214,25 @@ __device__ __forceinline__ bool verify_candidate(const uint8_t *hay, const uint8
 // before it so that no load reaches past either range (at most four round trips for up to sixteen bytes).
 // (hb and nd are wave-uniform pointers, `off` the lane's 32-bit offset from hb: scalar base + vector offset addressing, one
 // address register per lane instead of a 64-bit pointer per load - this sits inside kernels that live on 80 vector registers)
-__device__ __forceinline__ bool same_bytes(const uint8_t *hb, uint32_t off, const uint8_t *nd, uint32_t count)
+template <bool FOLD = false>
+__device__ __forceinline__ bool same_bytes(const uint8_t *hb, uint32_t off, const uint8_t *nd, uint32_t count, uint32_t keepx4 = 0)
 {
     auto u32 = [](const uint8_t *p, uint32_t o) { return reinterpret_cast<const UnalignedU32 *>(p + o)->v; };
     // 4 <= len <= 16 bytes from `at` on: the first and the last dword (all of a range of up to 8 bytes), then the two in
     // between; one load per side in flight - two pairs at once cost the kernels two vector registers they do not have
     auto group = [&](uint32_t at, uint32_t len) {
         const uint32_t o3 = at + len - 4;
-        if (u32(hb, off + at) != u32(nd, at)) return false;
-        if (u32(hb, off + o3) != u32(nd, o3)) return false;
+        if (hay_u32<FOLD>(u32(hb, off + at), keepx4) != u32(nd, at)) return false;
+        if (hay_u32<FOLD>(u32(hb, off + o3), keepx4) != u32(nd, o3)) return false;
         if (len <= 8) return true;
         const uint32_t o1 = at + 4, o2 = at + len - 8;
-        if (u32(hb, off + o1) != u32(nd, o1)) return false;
-        return u32(hb, off + o2) == u32(nd, o2);
+        if (hay_u32<FOLD>(u32(hb, off + o1), keepx4) != u32(nd, o1)) return false;
+        return hay_u32<FOLD>(u32(hb, off + o2), keepx4) == u32(nd, o2);
     };
     if (count < 4) {                                    // 0 .. 3 bytes: first, middle, last
         if (count == 0) return true;
         const uint32_t mid = count >> 1, last = count - 1;
-        return (uint32_t)((hb[off] ^ nd[0]) | (hb[off + mid] ^ nd[mid]) | (hb[off + last] ^ nd[last])) == 0;
+        return (uint32_t)((hay_u8<FOLD>(hb[off], keepx4) ^ nd[0]) | (hay_u8<FOLD>(hb[off + mid], keepx4) ^ nd[mid]) | (hay_u8<FOLD>(hb[off + last], keepx4) ^ nd[last])) == 0;
     }
     for (uint32_t k = 0; k + 16 < count; k += 16)
         if (!group(k, 16)) return false;
@@ -533,9 +573,11 @@ struct VerifyArgs {
 
 // ALL (the all-matches kernels, scan_tiles<..., ALL = true>): no early exit - every flagged offset is verified, and bit 4j+t of
 // *mask is set for each match at byte 4j+t of the chunk (address order).  The range rule is the same.
-template <bool ONE_BYTE, bool ALL = false>
+// FOLD (with ALL only): the haystack bytes read here are folded (fold_ascii4) before they are compared; the needle is lower case.
+template <bool ONE_BYTE, bool ALL = false, bool FOLD = false>
 __device__ __forceinline__ bool verify_flags_walk(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
-                                                  const uint8_t *s_needle, uint64_t &where, uint64_t far_off, uint32_t *mask)
+                                                  const uint8_t *s_needle, uint64_t &where, uint64_t far_off, uint32_t *mask,
+                                                  uint32_t keepx4 = 0)
 {
     bool hit = false;
     // all 16 flags of the lane in one word: flag of byte 4j+t at bit 8t+j (bit 7 of byte t of g[j] >> (7-j))
@@ -551,9 +593,9 @@ __device__ __forceinline__ bool verify_flags_walk(const uint32_t g[4], uint64_t 
             const uint64_t a = chunk * 16 + (uint64_t)(j * 4 + (bit >> 3));
             const uint64_t i = a - pr.mis;              // wraps for bytes in front of the haystack
             if (i < va.end) {
-                if (ONE_BYTE) hit = va.hay[i] == (uint8_t)pr.n0x4;
-                else if (far_off != 0 && va.hay[i + far_off] != va.needle[far_off]) hit = false;   // the caller's far filter byte
-                else hit = verify_candidate(va.hay, va.needle, va.n, s_needle, i);
+                if (ONE_BYTE) hit = hay_u8<FOLD>(va.hay[i], keepx4) == (uint8_t)pr.n0x4;
+                else if (far_off != 0 && hay_u8<FOLD>(va.hay[i + far_off], keepx4) != va.needle[far_off]) hit = false;   // the caller's far filter byte
+                else hit = verify_candidate<FOLD>(va.hay, va.needle, va.n, s_needle, i, keepx4);
                 where = i;                              // lowest match of this lane when hit
                 if constexpr (ALL) {
                     if (hit) *mask |= 1u << (j * 4 + (bit >> 3));
@@ -572,13 +614,13 @@ __device__ __forceinline__ bool verify_flags(const uint32_t g[4], uint64_t chunk
 }
 
 // Every match among the lane's flags: bit k set <=> hay[chunk * 16 - mis + k ..) holds the needle (k < 16).
-template <bool ONE_BYTE>
+template <bool ONE_BYTE, bool FOLD = false>
 __device__ __forceinline__ uint32_t verify_flags_all(const uint32_t g[4], uint64_t chunk, const Problem &pr, const VerifyArgs &va,
-                                                     const uint8_t *s_needle, uint64_t far_off)
+                                                     const uint8_t *s_needle, uint64_t far_off, uint32_t keepx4 = 0)
 {
     uint64_t where = 0;
     uint32_t mask = 0;
-    (void)verify_flags_walk<ONE_BYTE, true>(g, chunk, pr, va, s_needle, where, far_off, &mask);
+    (void)verify_flags_walk<ONE_BYTE, true, FOLD>(g, chunk, pr, va, s_needle, where, far_off, &mask, keepx4);
     return mask;
 }
 
@@ -668,9 +710,11 @@ __device__ __forceinline__ bool exact_verify_piece(const u32x4 &A, const NextPie
 // every flag is settled, no early exit, and the result is the lane's match mask - bit t set <=> a match at window byte t, i.e. at
 // hay index chunk_wave * 16 - mis + 16 * lane + t: the lane's own offsets at bits 0..15, those handed over from the next lane at
 // bits 16 + t.  A flag is handed to ONE lane, so every offset is owned by exactly one lane.  Same range rule.
+// FOLD: A and np hold folded bytes already; the bytes that same_bytes reads from memory are folded there.
+template <bool FOLD = false>
 __device__ __forceinline__ uint32_t exact_verify_piece_all(const u32x4 &A, const NextPiece &np, const uint32_t g[4], uint64_t chunk_wave,
                                                            int lane, const Problem &pr, const VerifyArgs &va, const uint32_t cmp16[4],
-                                                           uint32_t exact)
+                                                           uint32_t exact, uint32_t keepx4 = 0)
 {
     // index of the needle's first byte for a candidate at stream byte t of this lane's window: ubase (wave-uniform; wraps for
     // chunks in front of the haystack) + 16 * lane + t
@@ -724,7 +768,7 @@ __device__ __forceinline__ uint32_t exact_verify_piece_all(const u32x4 &A, const
             for (int j = 0; j < 4; ++j) diff |= (__builtin_amdgcn_alignbyte(sw[j + 1], sw[j], r) ^ cmp16[j]) & M[j];
             if (diff != 0) continue;
         }
-        if (in_memory == 0 || same_bytes(hb, off, va.needle, in_memory)) mask |= 1u << t;
+        if (in_memory == 0 || same_bytes<FOLD>(hb, off, va.needle, in_memory, keepx4)) mask |= 1u << t;
     }
     return mask;
 }

@@ -94,13 +94,14 @@ struct AllTiles {
 };
 
 template <int Q, int MODE, bool ONE_BYTE, int U, int NTMODE, bool FIND = false, bool L8 = false, bool LAZY_ORDER = false,
-          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false>
+          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false, bool FOLD = false>
 __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_t *s_needle_block, uint64_t tile0,
                                            uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr)
 {
     static_assert(!L8 || (MODE == 0 && !FIND), "the 8-byte layout covers the single-stream bool kernels");
     static_assert(!ALL || (!FIND && !L8 && !LAZY_ORDER), "the all-matches mode has kernels of its own (scan_all_kernel)");
     static_assert(!LINES || ALL, "the matching-lines mode (lines_scan_kernel, lines_tiles.hpp) is built on the all-matches one");
+    static_assert(!FOLD || ALL, "case folding (nocase_kernels.hpp) exists for the all-matches and matching-lines modes");
     static_assert(Q != kQDynamic || (MODE == 0 && !L8), "a run-time window is for the single-stream kernels' three-byte phase");
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "single-stream kernels only");
     constexpr bool SHIFTED = MODE >= 2;
@@ -143,10 +144,16 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     // ALL: the match masks of the wave's pieces in the current tile (emit launches), and what happens at the end of every tile
     // LINES (lines_scan_kernel only): `sink` is the launch's LineTiles instead; the match masks are kept for every tile, next to the
     // delimiter masks of the same registers, and the end of a tile is line_tile_done's.
+    // FOLD (the nocase kernels only): the loaded registers are folded to lower case once, right behind the loads - both filter
+    // phases, the cross-lane path and the exact compare then work on folded bytes as they are - and whatever reads haystack bytes
+    // from memory folds them there.  The delimiter is NOT folded: its masks are taken from the raw registers, before the fold, and
+    // a delimiter that is an upper-case letter stays what it is in the folded registers too (keepx4: no occurrence runs across it).
     AllTiles *all = static_cast<AllTiles *>(sink);
     LineTiles *lines = static_cast<LineTiles *>(sink);
     uint32_t all_mask[U];
     uint32_t line_dm[U];
+    uint32_t keepx4 = 0;
+    if constexpr (FOLD && LINES) keepx4 = ((lines->delim_x4 & 0xFFu) - 'A') < 26u ? lines->delim_x4 : 0u;       // (wave-uniform)
     auto tile_done = [&](uint64_t tile) {
         if constexpr (LINES) {
             line_tile_done<U>(*lines, line_dm, all_mask, tile, (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64, lane, wave, wpb);
@@ -291,6 +298,23 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                     H = load_chunk<false>(pr.base, halo);
                 }
             }
+            if constexpr (FOLD && !LOADED) {                // (LOADED: the 8-byte layout's hand-over, which the folding kernels never take)
+                if (keepx4 == 0) {                          // every delimiter but 'A'..'Z': the plain fold
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {           // (in load order: each piece waits for its own load only)
+                        if constexpr (LINES) line_dm[u] = delimiter_bits(A[u], lines->delim_x4);
+                        fold_ascii_chunk(A[u]);
+                    }
+                    if (!ONE_BYTE) fold_ascii_chunk(H);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if constexpr (LINES) line_dm[u] = delimiter_bits(A[u], lines->delim_x4);
+                        fold_ascii_chunk_keep(A[u], keepx4);
+                    }
+                    if (!ONE_BYTE) fold_ascii_chunk_keep(H, keepx4);
+                }
+            }
             // the poll is issued behind the data loads and consumed after them
             stop = FIND || ALL ? 0 : poll_found(found, pr.epoch);
             if (FIND) best_now = uniform64(best_raw);
@@ -411,7 +435,8 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
         else if (full) run_phase1(std::false_type{}, std::true_type{});
         else run_phase1(std::false_type{}, std::false_type{});
         // (the delimiters are taken from every tile, candidates or not)
-        if constexpr (LINES) line_capture<U>(A, chunk0, lane, *lines, line_dm);
+        if constexpr (LINES && FOLD) line_clip<U>(chunk0, lane, *lines, line_dm);
+        else if constexpr (LINES) line_capture<U>(A, chunk0, lane, *lines, line_dm);
         if (FIND) {
             const uint64_t first = chunk0 * 16 > pr.mis ? chunk0 * 16 - pr.mis : 0;   // lowest index this wave can report
             if (best_now <= pr.find_base + first) {                                     // all of it lies right of a match
@@ -590,11 +615,11 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                         NextPiece np;
                         np.N = u + 1 < U ? A[u + 1] : H;
                         np.kind = u + 1 < U ? 1 : 0;
-                        mk = exact_verify_piece_all(A[u], np, g, chunk0 + 64 * u, lane, pr, va, tail16, exact_len);
+                        mk = exact_verify_piece_all<FOLD>(A[u], np, g, chunk0 + 64 * u, lane, pr, va, tail16, exact_len, keepx4);
                     } else {
                         stage_once();
                         const uint64_t far_off = MODE == 0 && !ONE_BYTE ? uniform64(cold()->far_off) : 0;
-                        mk = verify_flags_all<ONE_BYTE>(g, chunk0 + 64 * u + lane, pr, va, s_needle, far_off);
+                        mk = verify_flags_all<ONE_BYTE, FOLD>(g, chunk0 + 64 * u + lane, pr, va, s_needle, far_off, keepx4);
                     }
                     if constexpr (LINES) {
                         all_mask[u] = mk;
@@ -847,8 +872,9 @@ struct AllArgs {
 constexpr uint32_t kAllCount = 0, kAllCountPerWorkgroup = 1, kAllEmit = 2;
 
 // Contiguous tiles per workgroup (tiles_per_block >= 1), so that workgroup order is address order.  No entry peek, no flag poll.
-template <int Q, int MODE, bool ONE_BYTE>
-__global__ void __launch_bounds__(kMaxBlock) scan_all_kernel(const Problem pr, AllArgs aa, uint64_t tiles_per_block)
+// (the kernel's body, shared with its case-folding twin - nocase_kernels.hpp; `pr` is the kernel's first argument)
+template <int Q, int MODE, bool ONE_BYTE, bool FOLD>
+__device__ __forceinline__ void scan_all_body(const Problem &pr, const AllArgs &aa, uint64_t tiles_per_block)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_needle[];
     __shared__ uint32_t s_wave[kMaxWavesPerBlock];
@@ -868,7 +894,7 @@ __global__ void __launch_bounds__(kMaxBlock) scan_all_kernel(const Problem pr, A
         if (cnt == 0 || rank >= aa.capacity) return;
         at.rank = rank;
     }
-    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &at);
+    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, false, FOLD>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &at);
     if (aa.mode == kAllEmit) return;
     const uint32_t wc = wave_sum(at.lane_count);
     if (lane == 0) s_wave[wave] = wc;
@@ -879,6 +905,12 @@ __global__ void __launch_bounds__(kMaxBlock) scan_all_kernel(const Problem pr, A
         if (aa.mode == kAllCountPerWorkgroup) aa.wg_count[blockIdx.x] = sum;
         else if (sum != 0) __hip_atomic_fetch_add(aa.total, (uint64_t)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+template <int Q, int MODE, bool ONE_BYTE>
+__global__ void __launch_bounds__(kMaxBlock) scan_all_kernel(const Problem pr, AllArgs aa, uint64_t tiles_per_block)
+{
+    scan_all_body<Q, MODE, ONE_BYTE, false>(pr, aa, tiles_per_block);
 }
 
 }  // namespace ss

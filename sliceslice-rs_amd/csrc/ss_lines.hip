@@ -15,7 +15,7 @@
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_lines.h"
-#include "lines_launch.hpp"
+#include "lines_host.hpp"
 #include "matches_scratch.hpp"
 
 #include <algorithm>
@@ -111,7 +111,7 @@ int combine_parts(const LinesScratch &sc, size_t len, const LinesOut &o, bool em
 
 // Enqueues everything; *d_total = the scratch word that takes the total.  Preconditions: len >= 1, the needle holds no delimiter,
 // n <= len.
-int enqueue_lines(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, int delimiter, hipStream_t st, const LinesOut &o,
+int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, int delimiter, hipStream_t st, const LinesOut &o,
                   ScratchLease *lease, uint64_t **d_total)
 {
     const uint8_t *hay = static_cast<const uint8_t *>(d_hay);
@@ -151,13 +151,13 @@ int enqueue_lines(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t
     HIP_TRY(ss::launch_lines_plain(head, false, st));
     HIP_TRY(ss::launch_lines_plain(tail, false, st));
     ss::LineArgs la = {sum, pre, o.begin, o.end, o.number, o.capacity, ll.dlo, ll.dhi, ll.hshift, 1, (uint32_t)delimiter, ss::kLinesSum};
-    if (!ss::launch_scan_lines(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la))
+    if (!scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la))
         return fail(SS_ERR_ARGUMENT, "no lines kernel for mode %d, window %d", ll.mode, ll.q);
     HIP_TRY(hipGetLastError());
     if (int rc = combine_parts(sc, len, o, emit, st)) return rc;
     if (emit) {
         la.mode = ss::kLinesEmit;
-        (void)ss::launch_scan_lines(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la);
+        (void)scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la);
         HIP_TRY(hipGetLastError());
         if (ll.tail_begin < len) {              // (the head has nothing in front of it that could be pending)
             tail.mode = ss::kLinesEmit;
@@ -182,7 +182,7 @@ bool no_line(const ss_searcher *s, size_t len, int delimiter)
     return std::find(s->needle.begin(), s->needle.begin() + (long)s->n, (uint8_t)delimiter) != s->needle.begin() + (long)s->n;
 }
 
-int lines_blocking(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, const LinesOut &o,
+int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, const LinesOut &o,
                    uint64_t *lines)
 {
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
@@ -192,7 +192,7 @@ int lines_blocking(const ss_searcher *s, const void *d_haystack, size_t len, int
     if (int rc = get_per_device(s, &pd)) return rc;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
@@ -201,25 +201,22 @@ int lines_blocking(const ss_searcher *s, const void *d_haystack, size_t len, int
 }
 
 }  // namespace
-}  // namespace ssh
 
-using namespace ssh;
-
-extern "C" {
-
-int ss_count_lines_device(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, uint64_t *lines)
+// (lines_host.hpp: `scan` is launch_scan_lines, or its case-folding twin for ss_nocase.hip)
+int count_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
+                            void *hip_stream, uint64_t *lines)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
-    return lines_blocking(s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines);
 }
 
-int ss_count_lines_device_async(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream,
-                                uint64_t *d_lines)
+int count_lines_device_async_with(ss::ScanLinesFn scan, const char *name, const ss_searcher *s, const void *d_haystack, size_t len,
+                                  int delimiter, void *hip_stream, uint64_t *d_lines)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, d_lines)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (stream_is_capturing(st))
-        return fail(SS_ERR_ARGUMENT, "ss_count_lines_device_async keeps scratch that later calls take over and cannot be captured into a hipGraph");
+        return fail(SS_ERR_ARGUMENT, "%s keeps scratch that later calls take over and cannot be captured into a hipGraph", name);
     SearchGate gate(s);
     PerDevice *pd = nullptr;
     if (int rc = get_per_device(s, &pd)) return rc;
@@ -232,12 +229,12 @@ int ss_count_lines_device_async(const ss_searcher *s, const void *d_haystack, si
     o.d_total2 = d_lines;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
     return lease.release_on(st);
 }
 
-int ss_find_lines_device(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, uint64_t *d_begin,
-                         uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines)
+int find_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
+                           void *hip_stream, uint64_t *d_begin, uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
     LinesOut o;
@@ -245,7 +242,32 @@ int ss_find_lines_device(const ss_searcher *s, const void *d_haystack, size_t le
     o.end = d_end;
     o.number = d_number;
     o.capacity = capacity;
-    return lines_blocking(s, d_haystack, len, delimiter, hip_stream, o, lines);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, o, lines);
+}
+
+}  // namespace ssh
+
+using namespace ssh;
+
+extern "C" {
+
+int ss_count_lines_device(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, uint64_t *lines)
+{
+    return count_lines_device_with(ss::launch_scan_lines, s, d_haystack, len, delimiter, hip_stream, lines);
+}
+
+int ss_count_lines_device_async(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream,
+                                uint64_t *d_lines)
+{
+    return count_lines_device_async_with(ss::launch_scan_lines, "ss_count_lines_device_async", s, d_haystack, len, delimiter, hip_stream,
+                                         d_lines);
+}
+
+int ss_find_lines_device(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, uint64_t *d_begin,
+                         uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines)
+{
+    return find_lines_device_with(ss::launch_scan_lines, s, d_haystack, len, delimiter, hip_stream, d_begin, d_end, d_number, capacity,
+                                  lines);
 }
 
 }  // extern "C"

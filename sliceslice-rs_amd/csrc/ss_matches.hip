@@ -12,7 +12,7 @@
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_matches.h"
-#include "matches_launch.hpp"
+#include "matches_host.hpp"
 #include "matches_scratch.hpp"
 
 namespace ssh {
@@ -47,9 +47,9 @@ int plan_all(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len,
     return SS_OK;
 }
 
-int launch_all(const AllLaunch &al, hipStream_t st, const ss::AllArgs &aa)
+int launch_all(ss::ScanAllFn scan, const AllLaunch &al, hipStream_t st, const ss::AllArgs &aa)
 {
-    if (!ss::launch_scan_all(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa))
+    if (!scan(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa))
         return fail(SS_ERR_ARGUMENT, "no all-matches kernel for mode %d, window %d", al.mode, al.q);
     HIP_TRY(hipGetLastError());
     return SS_OK;
@@ -63,13 +63,10 @@ int check_args(const ss_searcher *s, const void *d_haystack, size_t len, const v
 }
 
 }  // namespace
-}  // namespace ssh
 
-using namespace ssh;
-
-extern "C" {
-
-int ss_count_device_async(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_count)
+// (matches_host.hpp: `scan` is launch_scan_all, or its case-folding twin for ss_nocase.hip)
+int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
+                            uint64_t *d_count)
 {
     if (int rc = check_args(s, d_haystack, len, d_count)) return rc;
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
@@ -86,10 +83,10 @@ int ss_count_device_async(const ss_searcher *s, const void *d_haystack, size_t l
     AllLaunch al;
     if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
     const ss::AllArgs aa = {d_count, nullptr, nullptr, nullptr, 0, ss::kAllCount};
-    return launch_all(al, st, aa);
+    return launch_all(scan, al, st, aa);
 }
 
-int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
+int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
 {
     if (int rc = check_args(s, d_haystack, len, count)) return rc;
     SearchGate gate(s);
@@ -105,7 +102,7 @@ int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, vo
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
     HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));
     const ss::AllArgs aa = {d_total, nullptr, nullptr, nullptr, 0, ss::kAllCount};
-    if (int rc = launch_all(al, st, aa)) return rc;
+    if (int rc = launch_all(scan, al, st, aa)) return rc;
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
@@ -113,8 +110,8 @@ int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, vo
     return SS_OK;
 }
 
-int ss_find_all_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_offsets,
-                       uint64_t capacity, uint64_t *count)
+int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
+                         uint64_t *d_offsets, uint64_t capacity, uint64_t *count)
 {
     if (int rc = check_args(s, d_haystack, len, count)) return rc;
     if (capacity && !d_offsets) return fail(SS_ERR_ARGUMENT, "offsets are NULL with a capacity of %llu", (unsigned long long)capacity);
@@ -142,17 +139,39 @@ int ss_find_all_device(const ss_searcher *s, const void *d_haystack, size_t len,
     uint64_t *d_rank = d_total + 1;
     uint32_t *d_wg = reinterpret_cast<uint32_t *>(d_rank + blocks);
     const ss::AllArgs counting = {nullptr, d_wg, nullptr, nullptr, 0, ss::kAllCountPerWorkgroup};
-    if (int rc = launch_all(al, st, counting)) return rc;
+    if (int rc = launch_all(scan, al, st, counting)) return rc;
     HIP_TRY(ss::launch_prefix(d_wg, blocks, d_rank, d_total, st));
     if (capacity) {
         const ss::AllArgs emitting = {nullptr, d_wg, d_rank, d_offsets, capacity, ss::kAllEmit};
-        if (int rc = launch_all(al, st, emitting)) return rc;
+        if (int rc = launch_all(scan, al, st, emitting)) return rc;
     }
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
     *count = *lease.sc.h;
     return SS_OK;
+}
+
+}  // namespace ssh
+
+using namespace ssh;
+
+extern "C" {
+
+int ss_count_device_async(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_count)
+{
+    return count_device_async_with(ss::launch_scan_all, s, d_haystack, len, hip_stream, d_count);
+}
+
+int ss_count_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
+{
+    return count_device_with(ss::launch_scan_all, s, d_haystack, len, hip_stream, count);
+}
+
+int ss_find_all_device(const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *d_offsets,
+                       uint64_t capacity, uint64_t *count)
+{
+    return find_all_device_with(ss::launch_scan_all, s, d_haystack, len, hip_stream, d_offsets, capacity, count);
 }
 
 }  // extern "C"

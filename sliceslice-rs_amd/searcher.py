@@ -116,6 +116,17 @@ LINES_ABI = {
     "ss_count_lines_device_async": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
     "ss_find_lines_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_nocase.h: every occurrence and the matching lines ignoring ASCII case - libsliceslice_hip_nocase.so only
+# (the lines library's objects plus the case-folding scans)
+NOCASE_ABI = {
+    "ss_searcher_new_nocase": (_int, [_vp, _sz, ctypes.POINTER(ctypes.c_void_p)]),
+    "ss_count_nocase_device": (_int, [_vp, _vp, _sz, _vp, _pu64]),
+    "ss_count_nocase_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_nocase_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_nocase_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64]),
+    "ss_count_lines_nocase_device_async": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
+    "ss_find_lines_nocase_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -215,12 +226,14 @@ def _load(path):
     _bind(L, MATCHES_ABI, strict=False)
     _bind(L, MATCHES_BATCHED_ABI, strict=False)
     _bind(L, LINES_ABI, strict=False)
+    _bind(L, NOCASE_ABI, strict=False)
     _bind(L, HOOKS_ABI, strict=False)
     L.has_hooks = hasattr(L, "ss_debug_fail_next_scans")
     L.has_service = hasattr(L, "ss_service_start")
     L.has_matches = hasattr(L, "ss_count_device")
     L.has_matches_batched = hasattr(L, "ss_count_batched")
     L.has_lines = hasattr(L, "ss_count_lines_device")
+    L.has_nocase = hasattr(L, "ss_count_nocase_device")
     return L
 
 
@@ -239,6 +252,7 @@ _service = None
 _matches = None
 _matches_batched = None
 _lines = None
+_nocase = None
 
 
 def tools_lib():
@@ -343,6 +357,42 @@ class lines_build:
         return False
 
 
+class nocase_build:
+    """``with ss.nocase_build():`` - inside the block ``lib()`` is libsliceslice_hip_nocase.so: every function of the lines library
+    (so the case-sensitive ``count`` / ``find_all`` / ``count_lines`` / ``find_lines`` of searchers created inside work too) plus
+    their forms ignoring ASCII case (include/sliceslice_hip_nocase.h: the same methods with ``ignore_case=True``, and
+    ``DynamicHipSearcher.new_nocase``).  Searchers belong to the library that made them, so those searchers must be created inside
+    the block; they keep working after it."""
+
+    def __enter__(self):
+        global _lib, _nocase
+        if _nocase is None:
+            _nocase = _load(_build.build_nocase())
+        self._saved, _lib = _lib, _nocase
+        return _nocase
+
+    def __exit__(self, *a):
+        global _lib
+        _lib = self._saved
+        return False
+
+
+def _nocase_lib(L):
+    if not getattr(L, "has_nocase", False):
+        raise SlicesliceError(SS_ERR_ARGUMENT, "ignore_case=True / new_nocase are not part of this library: they live in "
+                                               "libsliceslice_hip_nocase.so - create the searcher inside `with ss.nocase_build():`")
+    return L
+
+
+_FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
+
+
+def fold_ascii(data):
+    """``data`` with the bytes 'A'..'Z' replaced by 'a'..'z' and every other byte value as it is - the fold of the calls that
+    ignore ASCII case (``bytes.lower()``)."""
+    return bytes(data).translate(_FOLD_TABLE)
+
+
 def _lines_lib(L):
     if not getattr(L, "has_lines", False):
         raise SlicesliceError(SS_ERR_ARGUMENT, "count_lines / find_lines are not part of this library: they live in "
@@ -444,13 +494,16 @@ class _on_device_of:
 class DynamicHipSearcher:
     """GPU counterpart of ``sliceslice::x86::DynamicAvx2Searcher`` (src/x86.rs:405-525)."""
 
-    def __init__(self, needle, position=None):
+    def __init__(self, needle, position=None, nocase=False):
         nb = needle.astype(np.uint8).tobytes() if isinstance(needle, np.ndarray) else bytes(needle)
         k, addr, n = _host_view(nb)
         self._h = ctypes.c_void_p()
         self._needle = nb
         L = self._L = lib()                 # the build this searcher belongs to (see tuning_build)
-        if position is None:
+        if nocase:
+            _check(_nocase_lib(L).ss_searcher_new_nocase(addr, n, ctypes.byref(self._h)), L)
+            self._needle = fold_ascii(nb)   # (the library's copy is the folded one)
+        elif position is None:
             _check(L.ss_searcher_new(addr, n, ctypes.byref(self._h)), L)
         else:
             _check(L.ss_searcher_with_position(addr, n, position % (1 << 64), ctypes.byref(self._h)), L)
@@ -466,6 +519,12 @@ class DynamicHipSearcher:
     @classmethod
     def with_position(cls, needle, position):
         return cls(needle, position)
+
+    @classmethod
+    def new_nocase(cls, needle):
+        """ss_searcher_new_nocase (inside ``with ss.nocase_build():``): an ordinary searcher for ``fold_ascii(needle)`` - what the
+        ``ignore_case=True`` forms of count / find_all / count_lines / find_lines take."""
+        return cls(needle, nocase=True)
 
     @property
     def needle(self):
@@ -545,80 +604,88 @@ class DynamicHipSearcher:
             raise TypeError("device haystack must be a contiguous 1-byte tensor")
         return haystack.data_ptr(), haystack.numel(), haystack
 
-    def count(self, haystack, stream=None):
-        """int: the number of (overlapping) occurrences of the needle in ``haystack`` (ss_count_device).  Empty needle: len + 1."""
-        L = _matches_lib(self._L)
+    def count(self, haystack, stream=None, ignore_case=False):
+        """int: the number of (overlapping) occurrences of the needle in ``haystack`` (ss_count_device).  Empty needle: len + 1.
+        ignore_case=True (here and in the seven methods below; searchers made inside ``with ss.nocase_build():`` from a needle
+        without upper-case bytes - ``new_nocase`` folds one): haystack letters match in either case (ss_count_nocase_device)."""
+        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck(L.ss_count_device(self._h, ptr, length, st, ctypes.byref(c)))
+            self._ck((L.ss_count_nocase_device if ignore_case else L.ss_count_device)(self._h, ptr, length, st, ctypes.byref(c)))
         return c.value
 
-    def count_async(self, haystack, d_count, stream=None):
+    def count_async(self, haystack, d_count, stream=None, ignore_case=False):
         """Enqueue only (ss_count_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        L = _matches_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck(L.ss_count_device_async(self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
+            self._ck((L.ss_count_nocase_device_async if ignore_case else L.ss_count_device_async)(
+                self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
 
-    def find_all(self, haystack, capacity=None, stream=None):
+    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False):
         """int64 tensor on the haystack's device: the offsets of every (overlapping) occurrence in ascending order
         (ss_find_all_device).  capacity=None: counted first, then exactly that many; else the leftmost ``capacity`` of them."""
         import torch
-        L = _matches_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
+        count_fn, find_fn = (L.ss_count_nocase_device, L.ss_find_all_nocase_device) if ignore_case else (L.ss_count_device, L.ss_find_all_device)
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         total = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
             if capacity is None:
-                self._ck(L.ss_count_device(self._h, ptr, length, st, ctypes.byref(total)))
+                self._ck(count_fn(self._h, ptr, length, st, ctypes.byref(total)))
                 capacity = total.value
             out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
-            self._ck(L.ss_find_all_device(self._h, ptr, length, st, out.data_ptr() if capacity else None, int(capacity),
-                                          ctypes.byref(total)))
+            self._ck(find_fn(self._h, ptr, length, st, out.data_ptr() if capacity else None, int(capacity),
+                             ctypes.byref(total)))
         return out[:min(int(capacity), total.value)]
 
-    def find_all_into(self, haystack, d_offsets, stream=None):
+    def find_all_into(self, haystack, d_offsets, stream=None, ignore_case=False):
         """ss_find_all_device into a caller's 8-byte device tensor (capacity = its length); returns the total count."""
-        L = _matches_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck(L.ss_find_all_device(self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None,
-                                          d_offsets.numel(), ctypes.byref(total)))
+            self._ck((L.ss_find_all_nocase_device if ignore_case else L.ss_find_all_device)(
+                self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None, d_offsets.numel(), ctypes.byref(total)))
         return total.value
 
     # -- the lines that contain the needle (libsliceslice_hip_lines.so: searchers made inside `with ss.lines_build():`) ------
-    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False):
         """int: the number of lines of ``haystack`` (cut at every ``delimiter`` byte) that hold at least one occurrence of the
-        needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines."""
-        L = _lines_lib(self._L)
+        needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines.  ignore_case=True folds the
+        haystack's letters, never the delimiter."""
+        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck(L.ss_count_lines_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
+            self._ck((L.ss_count_lines_nocase_device if ignore_case else L.ss_count_lines_device)(
+                self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
         return c.value
 
-    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None):
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False):
         """Enqueue only (ss_count_lines_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        L = _lines_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck(L.ss_count_lines_device_async(self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st,
-                                                   d_count.data_ptr()))
+            self._ck((L.ss_count_lines_nocase_device_async if ignore_case else L.ss_count_lines_device_async)(
+                self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
 
-    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False):
         """(begin, end, number): three int64 tensors on the haystack's device, one entry per matching line in ascending order - the
         offset of its first byte, the offset of the delimiter that closes it (len for a last line without one) and its 1-based
         line number (ss_find_lines_device).  capacity=None: counted first (ss_count_lines_device: one more pass over the haystack, as
         ``find_all`` does), then exactly that many; with a capacity the haystack is read at most twice and the leftmost ``capacity``
         records come back."""
         import torch
-        L = _lines_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
+        count_fn, find_fn = ((L.ss_count_lines_nocase_device, L.ss_find_lines_nocase_device) if ignore_case else
+                             (L.ss_count_lines_device, L.ss_find_lines_device))
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         d = _delimiter_byte(delimiter)
@@ -626,24 +693,24 @@ class DynamicHipSearcher:
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
             if capacity is None:
-                self._ck(L.ss_count_lines_device(self._h, ptr, length, d, st, ctypes.byref(total)))
+                self._ck(count_fn(self._h, ptr, length, d, st, ctypes.byref(total)))
                 capacity = total.value
             out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
             p = [out[k].data_ptr() if capacity else None for k in range(3)]
-            self._ck(L.ss_find_lines_device(self._h, ptr, length, d, st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
+            self._ck(find_fn(self._h, ptr, length, d, st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
         k = min(int(capacity), total.value)
         return out[0, :k], out[1, :k], out[2, :k]
 
-    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False):
         """ss_find_lines_device into the caller's 8-byte device tensors (each may be None: not wanted); returns the total count."""
-        L = _lines_lib(self._L)
+        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
             p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
-            self._ck(L.ss_find_lines_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
-                                            ctypes.byref(total)))
+            self._ck((L.ss_find_lines_nocase_device if ignore_case else L.ss_find_lines_device)(
+                self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
         return total.value
 
     # -- tuning / measurement hooks ------------------------------------------------------------------
@@ -765,23 +832,23 @@ class MemchrHipSearcher:
     def find(self, haystack, stream=None):
         return self._inner.find(haystack, stream)
 
-    def count(self, haystack, stream=None):
-        return self._inner.count(haystack, stream)
+    def count(self, haystack, stream=None, ignore_case=False):
+        return self._inner.count(haystack, stream, ignore_case)
 
-    def find_all(self, haystack, capacity=None, stream=None):
-        return self._inner.find_all(haystack, capacity, stream)
+    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False):
+        return self._inner.find_all(haystack, capacity, stream, ignore_case)
 
-    def count_lines(self, haystack, delimiter=b"\n", stream=None):
-        return self._inner.count_lines(haystack, delimiter, stream)
+    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False):
+        return self._inner.count_lines(haystack, delimiter, stream, ignore_case)
 
-    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None):
-        return self._inner.count_lines_async(haystack, d_count, delimiter, stream)
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False):
+        return self._inner.count_lines_async(haystack, d_count, delimiter, stream, ignore_case)
 
-    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
-        return self._inner.find_lines(haystack, delimiter, capacity, stream)
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False):
+        return self._inner.find_lines(haystack, delimiter, capacity, stream, ignore_case)
 
-    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
-        return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream)
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False):
+        return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case)
 
 
 def shard_range(length, needle_len, nranks, rank):

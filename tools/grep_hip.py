@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
-"""./grep_hip.py <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
+"""./grep_hip.py [-i] <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
 "hip" backend: map the file, build one searcher, one search_in, print the boolean.
   --count        the number of (overlapping) OCCURRENCES, not lines (libsliceslice_hip_matches.so, ss_count_device)
   --offsets      grep -b -o style: one byte offset per occurrence, ascending (ss_find_all_device)
   --count-lines  grep -c: the number of LINES that contain the needle (libsliceslice_hip_lines.so, ss_count_lines_device)
   --lines        grep -n: `number:line` for every line that contains the needle (ss_find_lines_device; only the records and the
                  bytes of those lines travel to the host)
+  -i, --ignore-case  with one of the four switches above: ASCII letters match in either case, every other byte exactly (grep -i
+                 in the C locale; libsliceslice_hip_nocase.so, the ss_*_nocase_device calls).  The line delimiter is not folded.
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
-per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched)."""
+per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched).  The batched
+library has no case-folding form: -i with -e / -f is refused."""
 import os
 import sys
 
@@ -30,11 +33,11 @@ def count_patterns(patterns, filename):
         return counts.cpu().tolist()
 
 
-def matching_lines(searcher, data):
+def matching_lines(searcher, data, ignore_case=False):
     """[(number, line bytes)] of the lines that contain the needle: the records, then only those byte ranges, come to the host."""
     import torch
     hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
-    begin, end, number = searcher.find_lines(hay)
+    begin, end, number = searcher.find_lines(hay, ignore_case=ignore_case)
     if begin.numel() == 0:
         return []
     # gather the matching lines' bytes on the device: one copy of sum(end - begin) bytes instead of the whole file
@@ -59,16 +62,38 @@ def main():
             patterns += [l for l in open(next(it), "rb").read().split(b"\n") if l]
         else:
             argv.append(a)
+    fold = "-i" in argv or "--ignore-case" in argv
+    argv = [a for a in argv if a not in ("-i", "--ignore-case")]
     args = [a for a in argv if not a.startswith("--")]
     flags = {a for a in argv if a.startswith("--")}
     if patterns:
+        if fold:
+            raise SystemExit("./grep_hip.py: -i is not available with -e / -f: several patterns go through the batched library, "
+                             "which has no case-folding form - run one pattern per call")
         if len(args) != 1 or flags != {"--count"}:
             raise SystemExit("./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file>")
         sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
         return
     if len(args) < 2 or flags - {"--count", "--offsets", "--count-lines", "--lines", "--rare-position"}:
-        raise SystemExit("./grep_hip.py <needle> <file> [--count | --offsets | --count-lines | --lines]")
+        raise SystemExit("./grep_hip.py [-i | --ignore-case] <needle> <file> [--count | --offsets | --count-lines | --lines]")
     needle, filename = args[0].encode(), args[1]
+    if fold:
+        if not flags & {"--count", "--offsets", "--count-lines", "--lines"}:
+            raise SystemExit("./grep_hip.py: -i needs one of --count, --offsets, --count-lines, --lines (the early-exit search has no "
+                             "case-folding form)")
+        with ss.nocase_build():
+            searcher = ss.DynamicHipSearcher.new_nocase(needle)
+        data = open(filename, "rb").read()
+        if "--lines" in flags:
+            for n, line in matching_lines(searcher, data, ignore_case=True):
+                sys.stdout.buffer.write(b"%d:%s\n" % (n, line))
+        elif "--count-lines" in flags:
+            print(searcher.count_lines(data, ignore_case=True))
+        elif "--offsets" in flags:
+            sys.stdout.write("".join("%d\n" % o for o in searcher.find_all(data, ignore_case=True).cpu().tolist()))
+        else:
+            print(searcher.count(data, ignore_case=True))
+        return
     if "--count-lines" in flags or "--lines" in flags:
         with ss.lines_build():
             searcher = ss.DynamicHipSearcher.new(needle)
