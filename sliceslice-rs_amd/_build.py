@@ -1,16 +1,9 @@
 """Builds csrc/ into the in-tree C-ABI libraries with hipcc for gfx950 (cross-compiles without a GPU).
 
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
-    libsliceslice_hip_service.so  the product's objects plus the resident search service (include/sliceslice_hip_service.h): an
-                                  opt-in component outside the hot path - a process uses one library or the other
-    libsliceslice_hip_matches.so  the product's objects plus the all-matches scan (include/sliceslice_hip_matches.h: count and
-                                  find-all): opt-in like the service - a process uses one library or the other
-    libsliceslice_hip_matches_batched.so  the matches library's objects plus the batched all-matches scan
-                                  (include/sliceslice_hip_matches_batched.h: count and find-all for a batch of problems): opt-in too
-    libsliceslice_hip_lines.so    the matches library's objects plus the matching-lines scan (include/sliceslice_hip_lines.h: count
-                                  and list the lines that contain a needle): opt-in too
-    libsliceslice_hip_nocase.so   the lines library's objects plus the case-folding scans (include/sliceslice_hip_nocase.h: count,
-                                  find-all and the matching lines ignoring ASCII case): opt-in too
+    libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES below (service, matches, matches_batched, lines, nocase): the
+                                  objects of the library's parent (the product's, where it has none) plus its own sources, which
+                                  define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
     libsliceslice_hip_tuning.so   the product's sources with -DSS_TUNING_VARIANTS -DSS_TEST_HOOKS: every kernel variant,
                                   ss_searcher_set_variant / _set_grid, fault injection (tools/, the variant and hook tests)
@@ -35,27 +28,35 @@ _CSRC = os.path.join(_HERE, "csrc")
 _ROOT = os.path.dirname(_HERE)
 _SO = os.path.join(_CSRC, "libsliceslice_hip.so")
 _TOOLS_SO = os.path.join(_CSRC, "libsliceslice_hip_tools.so")
-_SERVICE_SO = os.path.join(_CSRC, "libsliceslice_hip_service.so")
-_MATCHES_SO = os.path.join(_CSRC, "libsliceslice_hip_matches.so")
-_MATCHES_BATCHED_SO = os.path.join(_CSRC, "libsliceslice_hip_matches_batched.so")
-_LINES_SO = os.path.join(_CSRC, "libsliceslice_hip_lines.so")
-_NOCASE_SO = os.path.join(_CSRC, "libsliceslice_hip_nocase.so")
 # host-side translation units (ss_internal.hpp lists what each holds) ...
 _HOST_SOURCES = ["ss_core.hip", "ss_scan.hip", "ss_census.hip", "ss_host.hip", "ss_batched.hip", "ss_comm.hip"]
-_SERVICE_SOURCES = ["ss_service.hip"]       # NOT in the product: libsliceslice_hip_service.so and the hooks builds
-_MATCHES_SOURCES = ["ss_matches.hip", "scan_inst_all.hip"]     # NOT in the product: libsliceslice_hip_matches.so and ..._matches_batched.so
-_MATCHES_BATCHED_SOURCES = ["ss_matches_batched.hip", "scan_inst_all_batched.hip"]     # libsliceslice_hip_matches_batched.so only
-_LINES_SOURCES = ["ss_lines.hip", "scan_inst_lines.hip"]       # libsliceslice_hip_lines.so and ..._nocase.so
-_NOCASE_SOURCES = ["ss_nocase.hip", "scan_inst_nocase.hip"]    # libsliceslice_hip_nocase.so only
 # ... and the scan kernel family, one explicit-instantiation unit per (U, load flavour, search / find).  The product holds what
 # the constructors and ss_searcher_set_filter3 can select (scan_launch.hpp::kernel_built): U = 4, non-temporal loads.
 _KERNEL_SOURCES = ["scan_inst_u4_nt1.hip", "scan_inst_find_nt1.hip"]
 _SOURCES = _HOST_SOURCES + _KERNEL_SOURCES
+
+
+def _library(name, parent, sources, resources=True):
+    return {"parent": parent, "sources": sources, "so": os.path.join(_CSRC, "libsliceslice_hip_%s.so" % name),
+            "resources": os.path.join(_CSRC, "kernel_resources_%s.json" % name) if resources else None}
+
+
+# The opt-in libraries, none of them in the product: name -> its parent (None: the product), the sources it adds to its parent's,
+# its .so and the record of its kernels' registers.  The name is also that of its header (include/sliceslice_hip_<name>.h), of its
+# table and context manager in searcher.py (<NAME>_ABI, <name>_build) and of its lock file (.build_<name>.lock).
+LIBRARIES = {
+    "service": _library("service", None, ["ss_service.hip"], resources=False),       # (also in the hooks builds)
+    "matches": _library("matches", None, ["ss_matches.hip", "scan_inst_all.hip"]),
+    "matches_batched": _library("matches_batched", "matches", ["ss_matches_batched.hip", "scan_inst_all_batched.hip"]),
+    "lines": _library("lines", "matches", ["ss_lines.hip", "scan_inst_lines.hip"]),
+    "nocase": _library("nocase", "lines", ["ss_nocase.hip", "scan_inst_nocase.hip"]),
+}
+_SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
 _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
             "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "lines_scan_body.hpp", "lines_host.hpp", "matches_host.hpp",
-            "nocase_kernels.hpp", "nocase_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            "scan_choice.hpp", "nocase_kernels.hpp", "nocase_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_lines.h"),
@@ -80,42 +81,6 @@ def library_path():
 
 def tools_library_path():
     return _TOOLS_SO
-
-
-def service_library_path():
-    return _SERVICE_SO
-
-
-def matches_library_path():
-    return _MATCHES_SO
-
-
-def matches_resources_path():
-    return _MATCHES_RESOURCES
-
-
-def matches_batched_library_path():
-    return _MATCHES_BATCHED_SO
-
-
-def matches_batched_resources_path():
-    return _MATCHES_BATCHED_RESOURCES
-
-
-def lines_library_path():
-    return _LINES_SO
-
-
-def lines_resources_path():
-    return _LINES_RESOURCES
-
-
-def nocase_library_path():
-    return _NOCASE_SO
-
-
-def nocase_resources_path():
-    return _NOCASE_RESOURCES
 
 
 def native_bench_path():
@@ -217,10 +182,6 @@ def _build_variant(so, obj_suffix, extra_flags, link_flags, force, verbose, sour
 
 
 _RESOURCES = os.path.join(_CSRC, "kernel_resources.json")
-_MATCHES_RESOURCES = os.path.join(_CSRC, "kernel_resources_matches.json")
-_MATCHES_BATCHED_RESOURCES = os.path.join(_CSRC, "kernel_resources_matches_batched.json")
-_LINES_RESOURCES = os.path.join(_CSRC, "kernel_resources_lines.json")
-_NOCASE_RESOURCES = os.path.join(_CSRC, "kernel_resources_nocase.json")
 _RES_KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
              "Occupancy [waves/SIMD]": "waves_per_simd", "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills",
              "LDS Size [bytes/block]": "lds_bytes"}
@@ -265,78 +226,54 @@ def build(force=False, verbose=False):
     return so
 
 
-def build_service(force=False, verbose=False):
-    """The product's objects + csrc/ss_service.hip -> csrc/libsliceslice_hip_service.so (include/sliceslice_hip_service.h): the
-    resident search service is an opt-in component outside the hot path and ships apart from the drop-in library."""
-    build(verbose=verbose)                                  # the product's objects are shared
-    with _Lock(".build_service.lock"):
-        return _build_variant(_SERVICE_SO, ".o", [], [], force, verbose, _SOURCES + _SERVICE_SOURCES, own=_SERVICE_SOURCES)
+def _all_sources(name):
+    """The sources of library `name` and of every library it stands on, the product's first (None: the product's alone)."""
+    return _SOURCES if name is None else _all_sources(LIBRARIES[name]["parent"]) + LIBRARIES[name]["sources"]
 
 
-def build_matches(force=False, verbose=False):
-    """The product's objects + the all-matches scan (csrc/ss_matches.hip, scan_inst_all.hip) -> csrc/libsliceslice_hip_matches.so
-    (include/sliceslice_hip_matches.h).  The library's kernels are recorded in csrc/kernel_resources_matches.json."""
-    build(verbose=verbose)                                  # the product's objects (and their resource records) are shared
-    with _Lock(".build_matches.lock"):
-        return _build_variant(_MATCHES_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES, own=_MATCHES_SOURCES,
-                              record_resources=True, resources=_MATCHES_RESOURCES)
+def build_library(name, force=False, verbose=False):
+    """The objects of `name`'s parent (built first; they and their resource records are shared) + its own sources ->
+    csrc/libsliceslice_hip_<name>.so.  The kernels of the whole library are recorded in csrc/kernel_resources_<name>.json (the
+    service has no kernels of interest and no record)."""
+    lib = LIBRARIES[name]
+    if lib["parent"] is None:
+        build(verbose=verbose)
+    else:
+        build_library(lib["parent"], verbose=verbose)
+    with _Lock(".build_%s.lock" % name):
+        return _build_variant(lib["so"], ".o", [], [], force, verbose, _all_sources(name), own=lib["sources"],
+                              record_resources=lib["resources"] is not None, resources=lib["resources"])
 
 
-def matches_kernel_resources():
-    """Rows of csrc/kernel_resources_matches.json (written by build_matches()): the product's kernels and the all-matches ones."""
-    build_matches()
-    return json.load(open(_MATCHES_RESOURCES))
+def library_path_of(name):
+    return LIBRARIES[name]["so"]
 
 
-def build_matches_batched(force=False, verbose=False):
-    """The matches library's objects + the batched all-matches scan (csrc/ss_matches_batched.hip, scan_inst_all_batched.hip) ->
-    csrc/libsliceslice_hip_matches_batched.so (include/sliceslice_hip_matches_batched.h).  The library's kernels are recorded in
-    csrc/kernel_resources_matches_batched.json."""
-    build_matches(verbose=verbose)                          # the product's and the matches library's objects are shared
-    with _Lock(".build_matches_batched.lock"):
-        return _build_variant(_MATCHES_BATCHED_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES + _MATCHES_BATCHED_SOURCES,
-                              own=_MATCHES_BATCHED_SOURCES, record_resources=True, resources=_MATCHES_BATCHED_RESOURCES)
+def library_kernel_resources(name):
+    """Rows of csrc/kernel_resources_<name>.json (written by build_library(name)): the kernels of the library's parents and its own."""
+    build_library(name)
+    return json.load(open(LIBRARIES[name]["resources"]))
 
 
-def matches_batched_kernel_resources():
-    """Rows of csrc/kernel_resources_matches_batched.json (written by build_matches_batched()): the product's kernels, the
-    all-matches ones and the batched all-matches ones."""
-    build_matches_batched()
-    return json.load(open(_MATCHES_BATCHED_RESOURCES))
-
-
-def build_lines(force=False, verbose=False):
-    """The matches library's objects + the matching-lines scan (csrc/ss_lines.hip, scan_inst_lines.hip) ->
-    csrc/libsliceslice_hip_lines.so (include/sliceslice_hip_lines.h).  The library's kernels are recorded in
-    csrc/kernel_resources_lines.json."""
-    build_matches(verbose=verbose)                          # the product's and the matches library's objects are shared
-    with _Lock(".build_lines.lock"):
-        return _build_variant(_LINES_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES + _LINES_SOURCES,
-                              own=_LINES_SOURCES, record_resources=True, resources=_LINES_RESOURCES)
-
-
-def lines_kernel_resources():
-    """Rows of csrc/kernel_resources_lines.json (written by build_lines()): the product's kernels, the all-matches ones and the
-    matching-lines ones."""
-    build_lines()
-    return json.load(open(_LINES_RESOURCES))
-
-
-def build_nocase(force=False, verbose=False):
-    """The lines library's objects + the case-folding scans (csrc/ss_nocase.hip, scan_inst_nocase.hip) ->
-    csrc/libsliceslice_hip_nocase.so (include/sliceslice_hip_nocase.h).  The library's kernels are recorded in
-    csrc/kernel_resources_nocase.json."""
-    build_lines(verbose=verbose)                            # the product's, the matches and the lines library's objects are shared
-    with _Lock(".build_nocase.lock"):
-        return _build_variant(_NOCASE_SO, ".o", [], [], force, verbose, _SOURCES + _MATCHES_SOURCES + _LINES_SOURCES + _NOCASE_SOURCES,
-                              own=_NOCASE_SOURCES, record_resources=True, resources=_NOCASE_RESOURCES)
-
-
-def nocase_kernel_resources():
-    """Rows of csrc/kernel_resources_nocase.json (written by build_nocase()): the product's kernels, the all-matches ones, the
-    matching-lines ones and the case-folding ones."""
-    build_nocase()
-    return json.load(open(_NOCASE_RESOURCES))
+# The names tests, tools and __graft_entry__ call, one line each over the table.
+def build_service(force=False, verbose=False): return build_library("service", force, verbose)                    # noqa: E704
+def build_matches(force=False, verbose=False): return build_library("matches", force, verbose)                    # noqa: E704
+def build_matches_batched(force=False, verbose=False): return build_library("matches_batched", force, verbose)    # noqa: E704
+def build_lines(force=False, verbose=False): return build_library("lines", force, verbose)                        # noqa: E704
+def build_nocase(force=False, verbose=False): return build_library("nocase", force, verbose)                      # noqa: E704
+def service_library_path(): return library_path_of("service")                                                     # noqa: E704
+def matches_library_path(): return library_path_of("matches")                                                     # noqa: E704
+def matches_batched_library_path(): return library_path_of("matches_batched")                                     # noqa: E704
+def lines_library_path(): return library_path_of("lines")                                                         # noqa: E704
+def nocase_library_path(): return library_path_of("nocase")                                                       # noqa: E704
+def matches_resources_path(): return LIBRARIES["matches"]["resources"]                                            # noqa: E704
+def matches_batched_resources_path(): return LIBRARIES["matches_batched"]["resources"]                            # noqa: E704
+def lines_resources_path(): return LIBRARIES["lines"]["resources"]                                                # noqa: E704
+def nocase_resources_path(): return LIBRARIES["nocase"]["resources"]                                              # noqa: E704
+def matches_kernel_resources(): return library_kernel_resources("matches")                                        # noqa: E704
+def matches_batched_kernel_resources(): return library_kernel_resources("matches_batched")                        # noqa: E704
+def lines_kernel_resources(): return library_kernel_resources("lines")                                            # noqa: E704
+def nocase_kernel_resources(): return library_kernel_resources("nocase")                                          # noqa: E704
 
 
 def build_tools(force=False, verbose=False):

@@ -44,7 +44,7 @@ struct CombineArgs {
     uint64_t capacity;
 };
 
-// The matching-lines scan of one Problem (the kernel choice of launch_scan_all).  Returns false when no kernel fits.
+// The matching-lines scan of one Problem (the kernel choice of launch_scan_all: scan_choice.hpp).  Returns false when no kernel fits.
 bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
 // (the host side takes the scan as a value of this type: ss_lines.hip, lines_host.hpp)
 typedef bool (*ScanLinesFn)(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);

@@ -5,7 +5,7 @@
 namespace ss {
 
 // The all-matches scan of one Problem: mode 0 / 2 / 3 (3 runs the MODE 2 kernel), U = 4, non-temporal loads; sh.tpb >= 1
-// (contiguous tiles per workgroup).  Returns false when no kernel fits (nothing has been launched then).
+// (contiguous tiles per workgroup).  Returns false when no kernel fits (nothing has been launched then); scan_choice.hpp chooses.
 bool launch_scan_all(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa);
 // (the host side takes the scan as a value of this type: ss_matches.hip, matches_host.hpp)
 typedef bool (*ScanAllFn)(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa);

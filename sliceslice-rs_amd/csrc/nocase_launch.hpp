@@ -1,5 +1,5 @@
 // nocase_launch.hpp - host-side entry points of the case-folding scans (nocase_kernels.hpp; defined in scan_inst_nocase.hip, used
-// by ss_nocase.hip).  Same arguments, kernel choice and return value as launch_scan_all / launch_scan_lines.
+// by ss_nocase.hip).  Same arguments, kernel choice (scan_choice.hpp) and return value as launch_scan_all / launch_scan_lines.
 #pragma once
 #include "lines_launch.hpp"
 #include "matches_launch.hpp"

@@ -1,34 +1,17 @@
 // scan_inst_lines.hip - the matching-lines kernels (lines_kernels.hpp): one lines_scan_kernel per (Q, MODE, one-byte) combination
-// that find_all() has - 4 Q x MODE 0, 4 Q x MODE 2, one-byte: 9 - plus the plain, chunk and combine kernels.  Compiled into
+// that find_all() has - 4 Q x MODE 0, 4 Q x MODE 2, one-byte: 9, chosen by scan_choice.hpp - plus the plain, chunk and combine kernels.  Compiled into
 // libsliceslice_hip_lines.so only (ss_lines.hip is the host side).
 #include "lines_kernels.hpp"
+#include "scan_choice.hpp"
 
 namespace ss {
 
-namespace {
-
-template <int Q, int MODE, bool ONE_BYTE>
-void launch_lines_one(const Problem &pr, const Shape &sh, hipStream_t st, const LineArgs &la)
-{
-    const uint32_t dyn_lds = sh.lds_pad + (sh.block / kWave) * kNeedleLds;   // one needle slice per wave
-    lines_scan_kernel<Q, MODE, ONE_BYTE><<<dim3(sh.blocks), dim3(sh.block), dyn_lds, st>>>(pr, la, sh.tpb);
-}
-
-}  // namespace
-
 bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la)
 {
-    if (one_byte) return launch_lines_one<0, 0, true>(pr, sh, st, la), true;
-    if (mode == 3) mode = 2;                  // a pair-alone searcher: the MODE 2 kernel with its third byte, as find_all() does
-#define SS_CASE(QQ, MM)                                                                            \
-    case (QQ) * 4 + (MM):                                                                          \
-        return launch_lines_one<QQ, MM, false>(pr, sh, st, la), true;
-    switch (q * 4 + mode) {
-        SS_CASE(0, 0) SS_CASE(0, 2) SS_CASE(1, 0) SS_CASE(1, 2)
-        SS_CASE(2, 0) SS_CASE(2, 2) SS_CASE(3, 0) SS_CASE(3, 2)
-    }
-#undef SS_CASE
-    return false;
+    return choose_scan_kernel(q, mode, one_byte, [&](auto Q, auto MODE, auto ONE_BYTE) {
+        lines_scan_kernel<decltype(Q)::value, decltype(MODE)::value, decltype(ONE_BYTE)::value>
+            <<<dim3(sh.blocks), dim3(sh.block), scan_dyn_lds(sh), st>>>(pr, la, sh.tpb);
+    });
 }
 
 hipError_t launch_lines_plain(const PlainArgs &pa, bool every, hipStream_t st)

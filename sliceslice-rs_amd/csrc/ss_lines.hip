@@ -11,11 +11,12 @@
 //           lines read their bytes again and write the records at their rank.  A line longer than a tile, a workgroup's run or
 //           several of them is carried by the summaries alone.
 // The empty needle matches every line: the plain kernel in its EVERY form over the whole view, same combine.
-// The launch shape is ss_matches.hip's (the static one of an untuned search); the census is neither started nor read.
+// The launch shape is ss_matches.hip's (plan_static: the static one of an untuned search); the census is neither started nor read.
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_lines.h"
 #include "lines_host.hpp"
+#include "matches_host.hpp"
 #include "matches_scratch.hpp"
 
 #include <algorithm>
@@ -25,12 +26,8 @@ namespace {
 
 constexpr uint64_t kPlainPart = 64 * 1024;          // bytes per workgroup of the empty needle's pass
 
-// (ss_matches.hip, plan_all: the Problem and the shape of an untuned search)
-struct LinesLaunch {
-    ss::Problem pr;
-    ss::Shape shape;
-    int q = 0, mode = 0;
-    bool one_byte = false;
+// ss_matches.hip's plan with the tiles per workgroup capped and the edges of the filter stream
+struct LinesLaunch : StaticPlan {
     uint64_t head_end = 0, tail_begin = 0;          // hay [0, head_end) and [tail_begin, len) are not part of the filter stream
     uint64_t dlo = 0, dhi = 0;
     int64_t hshift = 0;
@@ -38,30 +35,20 @@ struct LinesLaunch {
 
 int plan_lines(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, LinesLaunch *out)
 {
-    ProblemShape ps;
-    fill_problem(s, pd->d_needle, d_hay, len, 0, &out->pr, &ps, nullptr);
-    const int occ = guess_workgroups_per_cu(s, out->pr, ps);
-    out->mode = out->pr.d == 0 ? 0 : 2;
-    out->one_byte = ps.one_byte;
-    out->q = (int)((ps.position % 16) / 4);
-    const unsigned block = ss::kBlock;
-    const uint64_t per_tile = (block / ss::kWave) * 4;                  // pieces per tile at U = 4
-    const uint64_t ntiles = (out->pr.npieces + per_tile - 1) / per_tile;
-    uint64_t tpb = 0, blocks = 0;
-    if (int rc = launch_grid(pd->dev, out->mode, ntiles, &tpb, &blocks)) return rc;
-    if (tpb > (uint64_t)ss::kLineTilesPerBlock) {
+    if (int rc = plan_static(s, pd, d_hay, len, out)) return rc;
+    if (out->shape.tpb > (uint64_t)ss::kLineTilesPerBlock) {
         // a workgroup keeps its waves' summaries of at most kLineTilesPerBlock tiles in LDS: whatever launch_grid's tuning prefers,
         // the answer must not depend on it
-        tpb = ss::kLineTilesPerBlock;
-        blocks = (ntiles + tpb - 1) / tpb;
+        const uint64_t blocks = (out->ntiles + ss::kLineTilesPerBlock - 1) / ss::kLineTilesPerBlock;
         if (blocks > 0x7fffffffull)
             return fail(SS_ERR_ARGUMENT, "a haystack of %zu bytes needs %llu workgroups of %d tiles; a grid holds 2^31 - 1", len,
                         (unsigned long long)blocks, ss::kLineTilesPerBlock);
+        out->shape.tpb = ss::kLineTilesPerBlock;
+        out->shape.blocks = (unsigned)blocks;
     }
-    out->shape = {(unsigned)blocks, block, tpb, occupancy_pad(occ, block)};
     // stream position a holds hay[a + fa - mis]; every wave of every tile loads its chunks below nchunks_all
-    const uint64_t fa = ps.fa, mis = out->pr.mis;
-    const uint64_t covered = std::min(ntiles * per_tile * 1024, out->pr.nchunks_all * 16);
+    const uint64_t fa = out->ps.fa, mis = out->pr.mis;
+    const uint64_t covered = std::min(out->ntiles * kPiecesPerTile * 1024, out->pr.nchunks_all * 16);
     out->hshift = (int64_t)fa - (int64_t)mis;
     out->head_end = fa > mis ? fa - mis : 0;
     out->tail_begin = std::min<uint64_t>(len, (uint64_t)((int64_t)covered + out->hshift));
@@ -169,8 +156,7 @@ int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, con
 
 int check_args(const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, const void *out)
 {
-    if (!s || !out) return fail(SS_ERR_ARGUMENT, "NULL argument");
-    if (len && !d_haystack) return fail(SS_ERR_ARGUMENT, "haystack is NULL");
+    if (int rc = check_common_args(s, d_haystack, len, out)) return rc;
     if (delimiter < 0 || delimiter > 255) return fail(SS_ERR_ARGUMENT, "delimiter %d is not a byte (0 .. 255)", delimiter);
     return SS_OK;
 }

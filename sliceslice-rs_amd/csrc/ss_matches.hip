@@ -7,8 +7,9 @@
 //                emit pass over the same grid in which only the workgroups that hold one of the first `capacity` matches re-read
 //                their tiles and write their offsets at their rank.  Workgroups take contiguous runs of tiles, so workgroup order is
 //                address order and the offsets land sorted.
-// The launch shape is the static one of an untuned search (ss_scan.hip, enqueue_scan with autotune off); the census is neither
-// started nor read, so a searcher's tuning state is the same before and after these calls, and the answers cannot depend on it.
+// The launch shape is the static one of an untuned search (plan_static, which ss_lines.hip uses too; ss_scan.hip, enqueue_scan with
+// autotune off); the census is neither started nor read, so a searcher's tuning state is the same before and after these calls, and
+// the answers cannot depend on it.
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_matches.h"
@@ -16,49 +17,38 @@
 #include "matches_scratch.hpp"
 
 namespace ssh {
+
+// (matches_host.hpp)
+int plan_static(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, StaticPlan *out)
+{
+    fill_problem(s, pd->d_needle, d_hay, len, 0, &out->pr, &out->ps, nullptr);
+    const int occ = guess_workgroups_per_cu(s, out->pr, out->ps);
+    out->mode = out->pr.d == 0 ? 0 : 2;
+    out->one_byte = out->ps.one_byte;
+    out->q = (int)((out->ps.position % 16) / 4);
+    out->ntiles = (out->pr.npieces + kPiecesPerTile - 1) / kPiecesPerTile;
+    uint64_t tpb = 0, blocks = 0;
+    if (int rc = launch_grid(pd->dev, out->mode, out->ntiles, &tpb, &blocks)) return rc;
+    out->shape = {(unsigned)blocks, ss::kBlock, tpb, occupancy_pad(occ, ss::kBlock)};
+    return SS_OK;
+}
+
+int check_common_args(const ss_searcher *s, const void *d_haystack, size_t len, const void *out)
+{
+    if (!s || !out) return fail(SS_ERR_ARGUMENT, "NULL argument");
+    if (len && !d_haystack) return fail(SS_ERR_ARGUMENT, "haystack is NULL");
+    return SS_OK;
+}
+
 namespace {
 
 // (the call-owned scratch - Scratch, take_scratch, ScratchLease: matches_scratch.hpp, shared with ss_matches_batched.hip)
 
-// One all-matches launch of (searcher, haystack): the Problem (fill_problem, the searcher's own filter bytes) and the shape an
-// untuned search takes - workgroups per CU guessed from the needle, one or two contiguous tiles per workgroup (ss_scan.hip:
-// guess_workgroups_per_cu, launch_grid).
-struct AllLaunch {
-    ss::Problem pr;
-    ss::Shape shape;
-    int q = 0, mode = 0;
-    bool one_byte = false;
-};
-
-int plan_all(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, AllLaunch *out)
-{
-    ProblemShape ps;
-    fill_problem(s, pd->d_needle, d_hay, len, 0, &out->pr, &ps, nullptr);
-    const int occ = guess_workgroups_per_cu(s, out->pr, ps);
-    out->mode = out->pr.d == 0 ? 0 : 2;
-    out->one_byte = ps.one_byte;
-    out->q = (int)((ps.position % 16) / 4);
-    const unsigned block = ss::kBlock;
-    const uint64_t per_tile = (block / ss::kWave) * 4;                  // pieces per tile at U = 4
-    const uint64_t ntiles = (out->pr.npieces + per_tile - 1) / per_tile;
-    uint64_t tpb = 0, blocks = 0;
-    if (int rc = launch_grid(pd->dev, out->mode, ntiles, &tpb, &blocks)) return rc;
-    out->shape = {(unsigned)blocks, block, tpb, occupancy_pad(occ, block)};
-    return SS_OK;
-}
-
-int launch_all(ss::ScanAllFn scan, const AllLaunch &al, hipStream_t st, const ss::AllArgs &aa)
+int launch_all(ss::ScanAllFn scan, const StaticPlan &al, hipStream_t st, const ss::AllArgs &aa)
 {
     if (!scan(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa))
         return fail(SS_ERR_ARGUMENT, "no all-matches kernel for mode %d, window %d", al.mode, al.q);
     HIP_TRY(hipGetLastError());
-    return SS_OK;
-}
-
-int check_args(const ss_searcher *s, const void *d_haystack, size_t len, const void *out)
-{
-    if (!s || !out) return fail(SS_ERR_ARGUMENT, "NULL argument");
-    if (len && !d_haystack) return fail(SS_ERR_ARGUMENT, "haystack is NULL");
     return SS_OK;
 }
 
@@ -68,7 +58,7 @@ int check_args(const ss_searcher *s, const void *d_haystack, size_t len, const v
 int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
                             uint64_t *d_count)
 {
-    if (int rc = check_args(s, d_haystack, len, d_count)) return rc;
+    if (int rc = check_common_args(s, d_haystack, len, d_count)) return rc;
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     PerDevice *pd = nullptr;
@@ -80,23 +70,23 @@ int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void
     }
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint64_t), st));
     if (len < s->n) return SS_OK;
-    AllLaunch al;
-    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    StaticPlan al;
+    if (int rc = plan_static(s, pd, d_haystack, len, &al)) return rc;
     const ss::AllArgs aa = {d_count, nullptr, nullptr, nullptr, 0, ss::kAllCount};
     return launch_all(scan, al, st, aa);
 }
 
 int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
 {
-    if (int rc = check_args(s, d_haystack, len, count)) return rc;
+    if (int rc = check_common_args(s, d_haystack, len, count)) return rc;
     SearchGate gate(s);
     if (s->n == 0) { *count = (uint64_t)len + 1; return SS_OK; }
     if (len < s->n) { *count = 0; return SS_OK; }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     PerDevice *pd = nullptr;
     if (int rc = get_per_device(s, &pd)) return rc;
-    AllLaunch al;
-    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    StaticPlan al;
+    if (int rc = plan_static(s, pd, d_haystack, len, &al)) return rc;
     ScratchLease lease;
     if (int rc = take_scratch(pd->dev, sizeof(uint64_t), &lease.sc, st)) return rc;
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
@@ -113,7 +103,7 @@ int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_ha
 int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
                          uint64_t *d_offsets, uint64_t capacity, uint64_t *count)
 {
-    if (int rc = check_args(s, d_haystack, len, count)) return rc;
+    if (int rc = check_common_args(s, d_haystack, len, count)) return rc;
     if (capacity && !d_offsets) return fail(SS_ERR_ARGUMENT, "offsets are NULL with a capacity of %llu", (unsigned long long)capacity);
     SearchGate gate(s);
     if (len < s->n) { *count = 0; return SS_OK; }
@@ -129,8 +119,8 @@ int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d
     }
     PerDevice *pd = nullptr;
     if (int rc = get_per_device(s, &pd)) return rc;
-    AllLaunch al;
-    if (int rc = plan_all(s, pd, d_haystack, len, &al)) return rc;
+    StaticPlan al;
+    if (int rc = plan_static(s, pd, d_haystack, len, &al)) return rc;
     const uint64_t blocks = al.shape.blocks;
     // [total u64][rank u64 x blocks][count u32 x blocks]
     ScratchLease lease;

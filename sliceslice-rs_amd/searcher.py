@@ -217,23 +217,46 @@ def _bind(L, table, strict):
     return L
 
 
+# What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
+# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES under their names, and the test hooks.
+_FEATURES = {
+    "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
+              "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
+              "`with ss.tuning_build():` or SLICESLICE_HIP_LIB=<path>)"),
+    "service": (SERVICE_ABI, "ss_service_start",
+                "the resident search service is not part of libsliceslice_hip.so: it lives in "
+                "libsliceslice_hip_service.so (`with ss.service_build():`, or SLICESLICE_HIP_LIB=<path>) "
+                "and in the hooks builds"),
+    "matches": (MATCHES_ABI, "ss_count_device",
+                "count / find_all are not part of libsliceslice_hip.so: they live in "
+                "libsliceslice_hip_matches.so - create the searcher inside `with ss.matches_build():`"),
+    "matches_batched": (MATCHES_BATCHED_ABI, "ss_count_batched",
+                        "count_batched / find_all_batched are not part of this library: they live in "
+                        "libsliceslice_hip_matches_batched.so - call them inside `with ss.matches_batched_build():`"),
+    "lines": (LINES_ABI, "ss_count_lines_device",
+              "count_lines / find_lines are not part of this library: they live in "
+              "libsliceslice_hip_lines.so - create the searcher inside `with ss.lines_build():`"),
+    "nocase": (NOCASE_ABI, "ss_count_nocase_device",
+               "ignore_case=True / new_nocase are not part of this library: they live in "
+               "libsliceslice_hip_nocase.so - create the searcher inside `with ss.nocase_build():`"),
+}
+
+
 def _load(path):
-    """One build of the library: every product symbol must be there; the hooks are bound where the build has them."""
+    """One build of the library: every product symbol must be there; the optional tables are bound where the build has them."""
     _preload_torch()
     L = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
     _bind(L, ABI, strict=True)
-    _bind(L, SERVICE_ABI, strict=False)
-    _bind(L, MATCHES_ABI, strict=False)
-    _bind(L, MATCHES_BATCHED_ABI, strict=False)
-    _bind(L, LINES_ABI, strict=False)
-    _bind(L, NOCASE_ABI, strict=False)
-    _bind(L, HOOKS_ABI, strict=False)
-    L.has_hooks = hasattr(L, "ss_debug_fail_next_scans")
-    L.has_service = hasattr(L, "ss_service_start")
-    L.has_matches = hasattr(L, "ss_count_device")
-    L.has_matches_batched = hasattr(L, "ss_count_batched")
-    L.has_lines = hasattr(L, "ss_count_lines_device")
-    L.has_nocase = hasattr(L, "ss_count_nocase_device")
+    for feature, (table, symbol, _) in _FEATURES.items():
+        _bind(L, table, strict=False)
+        setattr(L, "has_" + feature, hasattr(L, symbol))
+    return L
+
+
+def _feature_lib(L, feature):
+    """`L`, if that build of the library holds `feature` (a key of _FEATURES); else the error that says which build does."""
+    if not getattr(L, "has_" + feature, False):
+        raise SlicesliceError(SS_ERR_ARGUMENT, _FEATURES[feature][2])
     return L
 
 
@@ -247,12 +270,7 @@ def lib():
 
 
 _tools = None
-_tuning = None
-_service = None
-_matches = None
-_matches_batched = None
-_lines = None
-_nocase = None
+_loaded = {}          # _library_build: name -> the loaded library
 
 
 def tools_lib():
@@ -265,17 +283,19 @@ def tools_lib():
     return _tools
 
 
-class tuning_build:
-    """``with ss.tuning_build():`` - inside the block ``lib()`` is libsliceslice_hip_tuning.so (every kernel variant, the test
-    hooks of include/sliceslice_hip_tuning.h).  Objects remember the library they were made with, so searchers created
-    inside keep working (and are freed by the right library) after the block."""
+class _library_build:
+    """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES, or
+    "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
+    The subclasses below say what each library adds."""
+    name = None
 
     def __enter__(self):
-        global _lib, _tuning
-        if _tuning is None:
-            _tuning = _load(_build.build_tuning())
-        self._saved, _lib = _lib, _tuning
-        return _tuning
+        global _lib
+        if self.name not in _loaded:
+            _loaded[self.name] = _load(_build.build_tuning() if self.name == "tuning" else _build.build_library(self.name))
+        self._saved, _lib = _lib, _loaded[self.name]
+        return _lib
 
     def __exit__(self, *a):
         global _lib
@@ -283,105 +303,40 @@ class tuning_build:
         return False
 
 
-class service_build:
-    """``with ss.service_build():`` - inside the block ``lib()`` is libsliceslice_hip_service.so: every function of the product
-    library plus the resident search service (include/sliceslice_hip_service.h).  Searchers belong to the library that made
-    them, so the searchers a SearchService is asked about must be created inside the block too."""
-
-    def __enter__(self):
-        global _lib, _service
-        if _service is None:
-            _service = _load(_build.build_service())
-        self._saved, _lib = _lib, _service
-        return _service
-
-    def __exit__(self, *a):
-        global _lib
-        _lib = self._saved
-        return False
+class tuning_build(_library_build):
+    """libsliceslice_hip_tuning.so: every kernel variant and the test hooks of include/sliceslice_hip_tuning.h."""
+    name = "tuning"
 
 
-class matches_build:
-    """``with ss.matches_build():`` - inside the block ``lib()`` is libsliceslice_hip_matches.so: every function of the product
-    library plus the all-matches scan (include/sliceslice_hip_matches.h: ``count`` / ``find_all``).  Searchers belong to the library
-    that made them, so the searchers whose ``count`` / ``find_all`` are called must be created inside the block; they keep working
-    after it."""
-
-    def __enter__(self):
-        global _lib, _matches
-        if _matches is None:
-            _matches = _load(_build.build_matches())
-        self._saved, _lib = _lib, _matches
-        return _matches
-
-    def __exit__(self, *a):
-        global _lib
-        _lib = self._saved
-        return False
+class service_build(_library_build):
+    """libsliceslice_hip_service.so: the product library plus the resident search service (include/sliceslice_hip_service.h).  The
+    searchers a SearchService is asked about must be created inside the block too."""
+    name = "service"
 
 
-class matches_batched_build:
-    """``with ss.matches_batched_build():`` - inside the block ``lib()`` is libsliceslice_hip_matches_batched.so: every function of
-    the matches library (so ``count`` / ``find_all`` of searchers created inside work too) plus ``count_batched`` /
-    ``find_all_batched`` (include/sliceslice_hip_matches_batched.h), which must be called inside the block."""
-
-    def __enter__(self):
-        global _lib, _matches_batched
-        if _matches_batched is None:
-            _matches_batched = _load(_build.build_matches_batched())
-        self._saved, _lib = _lib, _matches_batched
-        return _matches_batched
-
-    def __exit__(self, *a):
-        global _lib
-        _lib = self._saved
-        return False
+class matches_build(_library_build):
+    """libsliceslice_hip_matches.so: the product library plus the all-matches scan (include/sliceslice_hip_matches.h: ``count`` /
+    ``find_all`` of searchers created inside the block)."""
+    name = "matches"
 
 
-class lines_build:
-    """``with ss.lines_build():`` - inside the block ``lib()`` is libsliceslice_hip_lines.so: every function of the matches library
-    (so ``count`` / ``find_all`` of searchers created inside work too) plus the matching-lines scan
-    (include/sliceslice_hip_lines.h: ``count_lines`` / ``find_lines``).  Searchers belong to the library that made them, so the
-    searchers whose ``count_lines`` / ``find_lines`` are called must be created inside the block; they keep working after it."""
-
-    def __enter__(self):
-        global _lib, _lines
-        if _lines is None:
-            _lines = _load(_build.build_lines())
-        self._saved, _lib = _lib, _lines
-        return _lines
-
-    def __exit__(self, *a):
-        global _lib
-        _lib = self._saved
-        return False
+class matches_batched_build(_library_build):
+    """libsliceslice_hip_matches_batched.so: the matches library plus ``count_batched`` / ``find_all_batched``
+    (include/sliceslice_hip_matches_batched.h), which must be called inside the block."""
+    name = "matches_batched"
 
 
-class nocase_build:
-    """``with ss.nocase_build():`` - inside the block ``lib()`` is libsliceslice_hip_nocase.so: every function of the lines library
-    (so the case-sensitive ``count`` / ``find_all`` / ``count_lines`` / ``find_lines`` of searchers created inside work too) plus
-    their forms ignoring ASCII case (include/sliceslice_hip_nocase.h: the same methods with ``ignore_case=True``, and
-    ``DynamicHipSearcher.new_nocase``).  Searchers belong to the library that made them, so those searchers must be created inside
-    the block; they keep working after it."""
-
-    def __enter__(self):
-        global _lib, _nocase
-        if _nocase is None:
-            _nocase = _load(_build.build_nocase())
-        self._saved, _lib = _lib, _nocase
-        return _nocase
-
-    def __exit__(self, *a):
-        global _lib
-        _lib = self._saved
-        return False
+class lines_build(_library_build):
+    """libsliceslice_hip_lines.so: the matches library plus the matching-lines scan (include/sliceslice_hip_lines.h: ``count_lines`` /
+    ``find_lines`` of searchers created inside the block)."""
+    name = "lines"
 
 
-def _nocase_lib(L):
-    if not getattr(L, "has_nocase", False):
-        raise SlicesliceError(SS_ERR_ARGUMENT, "ignore_case=True / new_nocase are not part of this library: they live in "
-                                               "libsliceslice_hip_nocase.so - create the searcher inside `with ss.nocase_build():`")
-    return L
+class nocase_build(_library_build):
+    """libsliceslice_hip_nocase.so: the lines library plus the forms ignoring ASCII case (include/sliceslice_hip_nocase.h:
+    ``ignore_case=True`` on ``count`` / ``find_all`` / ``count_lines`` / ``find_lines`` of searchers created inside the block, and
+    ``DynamicHipSearcher.new_nocase``)."""
+    name = "nocase"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -393,13 +348,6 @@ def fold_ascii(data):
     return bytes(data).translate(_FOLD_TABLE)
 
 
-def _lines_lib(L):
-    if not getattr(L, "has_lines", False):
-        raise SlicesliceError(SS_ERR_ARGUMENT, "count_lines / find_lines are not part of this library: they live in "
-                                               "libsliceslice_hip_lines.so - create the searcher inside `with ss.lines_build():`")
-    return L
-
-
 def _delimiter_byte(delimiter):
     """The one delimiter byte of count_lines / find_lines: an int 0..255 or a bytes object of length one."""
     if isinstance(delimiter, (bytes, bytearray)):
@@ -409,26 +357,12 @@ def _delimiter_byte(delimiter):
     return int(delimiter)
 
 
-def _matches_batched_lib():
-    L = lib()
-    if not getattr(L, "has_matches_batched", False):
-        raise SlicesliceError(SS_ERR_ARGUMENT, "count_batched / find_all_batched are not part of this library: they live in "
-                                               "libsliceslice_hip_matches_batched.so - call them inside `with ss.matches_batched_build():`")
-    return L
-
-
-def _matches_lib(L):
-    if not getattr(L, "has_matches", False):
-        raise SlicesliceError(SS_ERR_ARGUMENT, "count / find_all are not part of libsliceslice_hip.so: they live in "
-                                               "libsliceslice_hip_matches.so - create the searcher inside `with ss.matches_build():`")
-    return L
-
-
-def _hooks(L):
-    if not getattr(L, "has_hooks", False):
-        raise SlicesliceError(SS_ERR_ARGUMENT, "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
-                                               "`with ss.tuning_build():` or SLICESLICE_HIP_LIB=<path>)")
-    return L
+def _scan_fn(L, name, ignore_case):
+    """The function `name` of the matches or the lines library from `L`, or - ignore_case - its folding form from the nocase
+    library: ss_count_device -> ss_count_nocase_device, ss_find_lines_device -> ss_find_lines_nocase_device, ..."""
+    if ignore_case:
+        return getattr(_feature_lib(L, "nocase"), name.replace("_device", "_nocase_device"))
+    return getattr(_feature_lib(L, "lines" if "_lines_" in name else "matches"), name)
 
 
 def _check(rc, L=None):
@@ -501,7 +435,7 @@ class DynamicHipSearcher:
         self._needle = nb
         L = self._L = lib()                 # the build this searcher belongs to (see tuning_build)
         if nocase:
-            _check(_nocase_lib(L).ss_searcher_new_nocase(addr, n, ctypes.byref(self._h)), L)
+            _check(_feature_lib(L, "nocase").ss_searcher_new_nocase(addr, n, ctypes.byref(self._h)), L)
             self._needle = fold_ascii(nb)   # (the library's copy is the folded one)
         elif position is None:
             _check(L.ss_searcher_new(addr, n, ctypes.byref(self._h)), L)
@@ -608,28 +542,26 @@ class DynamicHipSearcher:
         """int: the number of (overlapping) occurrences of the needle in ``haystack`` (ss_count_device).  Empty needle: len + 1.
         ignore_case=True (here and in the seven methods below; searchers made inside ``with ss.nocase_build():`` from a needle
         without upper-case bytes - ``new_nocase`` folds one): haystack letters match in either case (ss_count_nocase_device)."""
-        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
+        fn = _scan_fn(self._L, "ss_count_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck((L.ss_count_nocase_device if ignore_case else L.ss_count_device)(self._h, ptr, length, st, ctypes.byref(c)))
+            self._ck(fn(self._h, ptr, length, st, ctypes.byref(c)))
         return c.value
 
     def count_async(self, haystack, d_count, stream=None, ignore_case=False):
         """Enqueue only (ss_count_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
+        fn = _scan_fn(self._L, "ss_count_device_async", ignore_case)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck((L.ss_count_nocase_device_async if ignore_case else L.ss_count_device_async)(
-                self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
+            self._ck(fn(self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
 
     def find_all(self, haystack, capacity=None, stream=None, ignore_case=False):
         """int64 tensor on the haystack's device: the offsets of every (overlapping) occurrence in ascending order
         (ss_find_all_device).  capacity=None: counted first, then exactly that many; else the leftmost ``capacity`` of them."""
         import torch
-        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
-        count_fn, find_fn = (L.ss_count_nocase_device, L.ss_find_all_nocase_device) if ignore_case else (L.ss_count_device, L.ss_find_all_device)
+        count_fn, find_fn = _scan_fn(self._L, "ss_count_device", ignore_case), _scan_fn(self._L, "ss_find_all_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         total = _u64(0)
@@ -645,13 +577,12 @@ class DynamicHipSearcher:
 
     def find_all_into(self, haystack, d_offsets, stream=None, ignore_case=False):
         """ss_find_all_device into a caller's 8-byte device tensor (capacity = its length); returns the total count."""
-        L = _nocase_lib(self._L) if ignore_case else _matches_lib(self._L)
+        fn = _scan_fn(self._L, "ss_find_all_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck((L.ss_find_all_nocase_device if ignore_case else L.ss_find_all_device)(
-                self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None, d_offsets.numel(), ctypes.byref(total)))
+            self._ck(fn(self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None, d_offsets.numel(), ctypes.byref(total)))
         return total.value
 
     # -- the lines that contain the needle (libsliceslice_hip_lines.so: searchers made inside `with ss.lines_build():`) ------
@@ -659,22 +590,20 @@ class DynamicHipSearcher:
         """int: the number of lines of ``haystack`` (cut at every ``delimiter`` byte) that hold at least one occurrence of the
         needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines.  ignore_case=True folds the
         haystack's letters, never the delimiter."""
-        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
+        fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck((L.ss_count_lines_nocase_device if ignore_case else L.ss_count_lines_device)(
-                self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
+            self._ck(fn(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
         return c.value
 
     def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False):
         """Enqueue only (ss_count_lines_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
+        fn = _scan_fn(self._L, "ss_count_lines_device_async", ignore_case)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
-            self._ck((L.ss_count_lines_nocase_device_async if ignore_case else L.ss_count_lines_device_async)(
-                self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
+            self._ck(fn(self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
 
     def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False):
         """(begin, end, number): three int64 tensors on the haystack's device, one entry per matching line in ascending order - the
@@ -683,9 +612,7 @@ class DynamicHipSearcher:
         ``find_all`` does), then exactly that many; with a capacity the haystack is read at most twice and the leftmost ``capacity``
         records come back."""
         import torch
-        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
-        count_fn, find_fn = ((L.ss_count_lines_nocase_device, L.ss_find_lines_nocase_device) if ignore_case else
-                             (L.ss_count_lines_device, L.ss_find_lines_device))
+        count_fn, find_fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case), _scan_fn(self._L, "ss_find_lines_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         d = _delimiter_byte(delimiter)
@@ -703,14 +630,13 @@ class DynamicHipSearcher:
 
     def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False):
         """ss_find_lines_device into the caller's 8-byte device tensors (each may be None: not wanted); returns the total count."""
-        L = _nocase_lib(self._L) if ignore_case else _lines_lib(self._L)
+        fn = _scan_fn(self._L, "ss_find_lines_device", ignore_case)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
             st = stream if stream is not None else _current_stream_handle()
             p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
-            self._ck((L.ss_find_lines_nocase_device if ignore_case else L.ss_find_lines_device)(
-                self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
+            self._ck(fn(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
         return total.value
 
     # -- tuning / measurement hooks ------------------------------------------------------------------
@@ -741,11 +667,11 @@ class DynamicHipSearcher:
     def set_variant(self, variant):
         """Tuning builds only (ss_searcher_set_variant); 0 - the automatic choice - is accepted by every build."""
         if int(variant) != 0 or getattr(self._L, "has_hooks", False):
-            self._ck(_hooks(self._L).ss_searcher_set_variant(self._h, int(variant)))
+            self._ck(_feature_lib(self._L, "hooks").ss_searcher_set_variant(self._h, int(variant)))
 
     def set_grid(self, blocks):
         if int(blocks) != 0 or getattr(self._L, "has_hooks", False):
-            self._ck(_hooks(self._L).ss_searcher_set_grid(self._h, int(blocks)))
+            self._ck(_feature_lib(self._L, "hooks").ss_searcher_set_grid(self._h, int(blocks)))
 
     def last_launch(self):
         """(workgroups per CU, workgroups in the grid) of the latest scan enqueued through this searcher on the current device."""
@@ -770,7 +696,7 @@ class DynamicHipSearcher:
         """Hooks builds: the census's per-position match counts {pair_match, triple_match, pair_lanes, triple_lanes}, or None."""
         c = (ctypes.c_uint32 * 131)()
         have = ctypes.c_int(0)
-        self._ck(_hooks(self._L).ss_debug_census_stats(self._h, haystack.data_ptr(), haystack.numel(), c, ctypes.byref(have)))
+        self._ck(_feature_lib(self._L, "hooks").ss_debug_census_stats(self._h, haystack.data_ptr(), haystack.numel(), c, ctypes.byref(have)))
         if not have.value:
             return None
         self.stats_roles = have.value - 1                   # the slot the pair counts were gathered for
@@ -780,7 +706,7 @@ class DynamicHipSearcher:
         """Hooks builds: the candidate census of (this searcher, haystack) as a dict, or None when its counts are not in."""
         c = (ctypes.c_uint32 * 11)()
         ptr, n = haystack.data_ptr(), haystack.numel()
-        self._ck(_hooks(self._L).ss_debug_census(self._h, ptr, n, c))
+        self._ck(_feature_lib(self._L, "hooks").ss_debug_census(self._h, ptr, n, c))
         self.last_mode = int(c[5])                          # kernel family of the latest launch (0, 2 or 3)
         self.device_filter = (int(c[6]), int(c[7]), int(c[8]))      # the bytes the device tests on this haystack
         self.triple_state, self.triple_trials = int(c[9]), int(c[10])  # 0 undecided / 1 own / 2 from the histogram; trials so far
@@ -896,7 +822,7 @@ class ShardedSearcher:
 
     def fail_next_scans(self, count=1):
         """Hooks builds: the next `count` scans of this rank fail before they reach the device (ss_debug_fail_next_scans)."""
-        self._ck(_hooks(self._L).ss_debug_fail_next_scans(self._searcher._h, count))
+        self._ck(_feature_lib(self._L, "hooks").ss_debug_fail_next_scans(self._searcher._h, count))
 
     def _init_rccl(self):
         import torch
@@ -1119,7 +1045,7 @@ class NodeSearcher:
 
     def set_epoch(self, value):
         """Hooks builds: move the set's "found" epoch (ss_debug_set_comm_epoch) so that a test can cross the 2^31 wrap."""
-        self._ck(_hooks(self._L).ss_debug_set_comm_epoch(None, self._set, value))
+        self._ck(_feature_lib(self._L, "hooks").ss_debug_set_comm_epoch(None, self._set, value))
 
     def shard_range(self, total_len, g):
         return shard_range(total_len, len(self.needle), len(self.devices), g)
@@ -1167,11 +1093,7 @@ class SearchService:
 
     def __init__(self, workgroups=0, lease_ms=0.0):
         self._h = ctypes.c_void_p()
-        L = self._L = lib()
-        if not getattr(L, "has_service", False):
-            raise SlicesliceError(SS_ERR_ARGUMENT, "the resident search service is not part of libsliceslice_hip.so: it lives in "
-                                                   "libsliceslice_hip_service.so (`with ss.service_build():`, or SLICESLICE_HIP_LIB=<path>) "
-                                                   "and in the hooks builds")
+        L = self._L = _feature_lib(lib(), "service")
         _check(L.ss_service_start(int(workgroups), float(lease_ms), ctypes.byref(self._h)), L)
 
     def _ck(self, rc):
@@ -1196,7 +1118,7 @@ class SearchService:
     def counters(self):
         """(requests served, kernel launches, requests that skipped the acquire) - hooks builds (ss_service_counters)."""
         r, k, t = _u64(0), _u64(0), _u64(0)
-        self._ck(_hooks(self._L).ss_service_counters(self._h, ctypes.byref(r), ctypes.byref(k), ctypes.byref(t)))
+        self._ck(_feature_lib(self._L, "hooks").ss_service_counters(self._h, ctypes.byref(r), ctypes.byref(k), ctypes.byref(t)))
         return r.value, k.value, t.value
 
     def stop(self):
@@ -1252,21 +1174,21 @@ class BatchPlan:
         """((first, second, third) indices in the needle, the packed bytes, slices that scan the problem) of one problem's
         descriptor - hooks builds (ss_debug_plan_filter)."""
         out = (ctypes.c_uint32 * 5)()
-        _check(_hooks(self._L).ss_debug_plan_filter(self._h, int(problem), out), self._L)
+        _check(_feature_lib(self._L, "hooks").ss_debug_plan_filter(self._h, int(problem), out), self._L)
         return (out[0], out[1], out[2]), out[3], out[4]
 
     def layout(self):
         """{"two": the plan holds two layouts, "slices": (first, second), "found_last": problems found in the latest tallied run,
         "next_is_second": the next run takes the contiguous-runs layout} - hooks builds (ss_debug_plan_layout)."""
         out = (ctypes.c_uint32 * 5)()
-        _check(_hooks(self._L).ss_debug_plan_layout(self._h, out), self._L)
+        _check(_feature_lib(self._L, "hooks").ss_debug_plan_layout(self._h, out), self._L)
         return {"two": bool(out[0]), "slices": (out[1], out[2]), "found_last": out[3], "next_is_second": bool(out[4])}
 
     def cold_of(self, problem):
         """(schedule indices, schedule bytes, exact_len, bytes in front, the compare's 16 bytes) of one problem's ready-made cold
         part - hooks builds (ss_debug_plan_cold)."""
         out = (ctypes.c_uint32 * 14)()
-        _check(_hooks(self._L).ss_debug_plan_cold(self._h, int(problem), out), self._L)
+        _check(_feature_lib(self._L, "hooks").ss_debug_plan_cold(self._h, int(problem), out), self._L)
         n = out[0]
         idx = b"".join(int(out[2 + t]).to_bytes(4, "little") for t in range(4))[:n]
         val = b"".join(int(out[6 + t]).to_bytes(4, "little") for t in range(4))[:n]
@@ -1291,7 +1213,7 @@ def batch_classes(haystacks, hay_off=None, hay_ranges=None):
     hb, _, count = _ranges(hay_off, *(hay_ranges or (None, None)))
     st, cls = ctypes.c_uint32(0), (ctypes.c_uint8 * 256)()
     L = lib()
-    _check(_hooks(L).ss_debug_batch_classes(haystacks.data_ptr(), hb, count, ctypes.byref(st), cls), L)
+    _check(_feature_lib(L, "hooks").ss_debug_batch_classes(haystacks.data_ptr(), hb, count, ctypes.byref(st), cls), L)
     return st.value, (list(cls) if st.value == 3 else None)
 
 
@@ -1337,7 +1259,7 @@ def count_batched(haystacks, hay_off, needles, needle_off, stream=None, hay_rang
     """(Overlapping) occurrences of needle i in haystack i for many problems in one call (ss_count_batched; inside
     ``with ss.matches_batched_build():``).  Arguments as search_batched.  Enqueue only; returns an int64 device tensor."""
     import torch
-    L = _matches_batched_lib()
+    L = _feature_lib(lib(), "matches_batched")
     hb, he, count = _ranges(hay_off, *(hay_ranges or (None, None)))
     nb, ne, ncount = _ranges(needle_off, *(needle_ranges or (None, None)))
     assert count == ncount
@@ -1353,7 +1275,7 @@ def find_all_batched(haystacks, hay_off, needles, needle_off, stream=None, hay_r
     min(total, capacity) entries; ``offsets[row_begin[i]:row_begin[i + 1]]`` are problem i's offsets relative to its own haystack,
     ascending (rows beyond ``capacity`` are cut).  capacity=None: counted first, then exactly that many.  Waits for the stream."""
     import torch
-    L = _matches_batched_lib()
+    L = _feature_lib(lib(), "matches_batched")
     hb, he, count = _ranges(hay_off, *(hay_ranges or (None, None)))
     nb, ne, ncount = _ranges(needle_off, *(needle_ranges or (None, None)))
     assert count == ncount
@@ -1420,7 +1342,7 @@ def choose_filter_for_position(needle, position):
     Hooks builds (a pure host function; a constructed searcher's `filter3` says the same in every build)."""
     nb = bytes(needle)
     a, b, c = _sz(0), _sz(0), _sz(0)
-    L = _hooks(lib())
+    L = _feature_lib(lib(), "hooks")
     _check(L.ss_choose_filter_for_position(nb, len(nb), position, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), L)
     return a.value, b.value, c.value
 

@@ -73,6 +73,23 @@ def rust_prototypes(source="hip.rs"):
     return protos
 
 
+def build_module():
+    return sys.modules["sliceslice_rs_amd._build"]
+
+
+def exported(path):
+    """names of the functions a shared library exports"""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
+
+
+def ctypes_class(t):
+    """pointer / integer width class of an entry of a ctypes table, as header_prototypes spells it"""
+    if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "ptr"
+    return {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]
+
+
 def test_header_parser_sees_every_symbol():
     protos = header_prototypes()
     assert sorted(protos) == sorted(ss.searcher.ABI)                 # the same set tests/test_host_logic.py checks in the .so
@@ -131,6 +148,38 @@ def test_ctypes_table_matches_the_header():
         # size_t and uint64_t are the same width on this ABI; the table may spell either
         norm = lambda p: (p[0].replace("usize", "u64"), [a.replace("usize", "u64") for a in p[1]])   # noqa: E731
         assert norm(got) == norm(want), (name, got, want)
+
+
+def test_every_library_of_the_table_has_its_header_table_context_flag_and_guard():
+    """_build.LIBRARIES is the one place a library is entered: everything else about it goes by its name."""
+    libraries = build_module().LIBRARIES
+    assert list(libraries) == ["service", "matches", "matches_batched", "lines", "nocase"]
+    product = ss.lib()
+    for name, entry in libraries.items():
+        assert entry["parent"] is None or entry["parent"] in libraries, name
+        assert os.path.basename(entry["so"]) == "libsliceslice_hip_%s.so" % name
+        assert all(os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", s)) for s in entry["sources"]), name
+        header = "sliceslice_hip_%s.h" % name
+        assert os.path.exists(os.path.join(ROOT, "include", header)), header
+        table = getattr(ss.searcher, name.upper() + "_ABI")
+        assert sorted(table) == sorted(header_prototypes(header)), name
+        assert ss.searcher._FEATURES[name][0] is table and ss.searcher._FEATURES[name][1] in table, name
+        context = getattr(ss, name + "_build")
+        assert not getattr(product, "has_" + name), name
+        with pytest.raises(ss.SlicesliceError, match=r"ss\.%s_build\(\)" % name) as e:
+            ss.searcher._feature_lib(product, name)
+        assert e.value.code == ss.SS_ERR_ARGUMENT
+        with context() as L:
+            assert ss.lib() is L and getattr(L, "has_" + name) and ss.searcher._feature_lib(L, name) is L, name
+            held, up = set(), name
+            while up is not None:                       # a library holds what it stands on, and nothing else of the table
+                held.add(up)
+                up = libraries[up]["parent"]
+            assert {n for n in libraries if getattr(L, "has_" + n)} == held, name
+            with ss.service_build() as inner:           # blocks nest and restore
+                assert ss.lib() is inner
+            assert ss.lib() is L
+        assert ss.lib() is product
 
 
 def _bench(args, env_extra=None):

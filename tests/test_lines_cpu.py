@@ -2,32 +2,20 @@
 symbol by symbol; libsliceslice_hip_lines.so exports exactly the three headers while the other libraries export what they did; the
 lines kernels meet the scan kernels' bar; the Python methods refuse outside lines_build(); the rule restated here reproduces
 tests/golden/lines_kat.json."""
-import ctypes
 import hashlib
 import json
 import os
 import re
 import struct
-import subprocess
-import sys
 
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import header_prototypes, rust_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class as norm, exported as _exported, header_prototypes, rust_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 LINES = ["ss_count_lines_device", "ss_count_lines_device_async", "ss_find_lines_device"]
-
-
-def _build():
-    return sys.modules["sliceslice_rs_amd._build"]
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
 
 
 def lines_rule(data, needle, delimiter):
@@ -51,8 +39,6 @@ def test_header_ctypes_and_rust_agree():
     assert c["ss_find_lines_device"] == ("i32", ["ptr", "ptr", "usize", "i32", "ptr", "ptr", "ptr", "ptr", "u64", "ptr"])
     r = rust_prototypes("hip_lines.rs")
     assert r == c, (r, c)
-    norm = lambda t: "ptr" if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))) else \
-        {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]           # noqa: E731
     for name, (res, args) in ss.searcher.LINES_ABI.items():
         got = (norm(res), [norm(a) for a in args])
         want = c[name]

@@ -3,29 +3,17 @@ Rust module agree symbol by symbol; libsliceslice_hip_matches_batched.so exports
 product and the matches library export none of the new two; the shared objects are the same objects (their kernels' rows in the
 new library's resource record equal the other records' rows); the new kernels meet the scan kernels' bar; Python refuses outside
 matches_batched_build()."""
-import ctypes
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import header_prototypes, rust_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class as norm, exported as _exported, header_prototypes, rust_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = "sliceslice_hip_matches_batched.h"
-
-
-def _build():
-    return sys.modules["sliceslice_rs_amd._build"]
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
 
 
 def test_header_ctypes_and_rust_agree():
@@ -35,8 +23,6 @@ def test_header_ctypes_and_rust_agree():
     assert c["ss_find_all_batched"] == ("i32", ["ptr"] * 6 + ["usize", "ptr", "ptr", "ptr", "ptr", "u64", "ptr"])
     r = rust_prototypes("hip_matches_batched.rs")
     assert r == c, (r, c)
-    norm = lambda t: "ptr" if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))) else \
-        {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]           # noqa: E731
     for name, (res, args) in ss.searcher.MATCHES_BATCHED_ABI.items():
         got = (norm(res), [norm(a) for a in args])
         want = c[name]

@@ -1,28 +1,16 @@
 """CPU checks of every-occurrence search (include/sliceslice_hip_matches.h): the header, the ctypes table and the Rust module agree
 symbol by symbol; libsliceslice_hip_matches.so exports exactly the product header plus the matches header while the product library
 exports none of it; the library's kernels meet the scan kernels' bar; the Python methods refuse outside matches_build()."""
-import ctypes
 import json
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import header_prototypes, rust_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class as norm, exported as _exported, header_prototypes, rust_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _build():
-    return sys.modules["sliceslice_rs_amd._build"]
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
 
 
 def test_header_ctypes_and_rust_agree():
@@ -32,8 +20,6 @@ def test_header_ctypes_and_rust_agree():
     assert c["ss_count_device"] == ("i32", ["ptr", "ptr", "usize", "ptr", "ptr"])
     r = rust_prototypes("hip_matches.rs")
     assert r == c, (r, c)
-    norm = lambda t: "ptr" if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))) else \
-        {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]           # noqa: E731
     for name, (res, args) in ss.searcher.MATCHES_ABI.items():
         got = (norm(res), [norm(a) for a in args])
         want = c[name]

@@ -2,7 +2,6 @@
 agree symbol by symbol; libsliceslice_hip_nocase.so exports exactly the four headers while the other libraries export what they did;
 the folding kernels meet the scan kernels' bar and live in no other library; the Python methods refuse outside nocase_build();
 fold_ascii is bytes.lower(); the rule restated here reproduces tests/golden/nocase_kat.json."""
-import ctypes
 import hashlib
 import json
 import os
@@ -14,8 +13,8 @@ import sys
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import header_prototypes, rust_prototypes
-from test_lines_cpu import _build, _exported, lines_rule
+from test_bindings_cpu import build_module as _build, ctypes_class as norm, exported as _exported, header_prototypes, rust_prototypes
+from test_lines_cpu import lines_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -65,8 +64,6 @@ def test_header_ctypes_and_rust_agree():
         assert c[model.replace("_device", "_nocase_device")] == protos[model], model
     r = rust_prototypes("hip_nocase.rs")
     assert r == c, (r, c)
-    norm = lambda t: "ptr" if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))) else \
-        {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]           # noqa: E731
     for name, (res, args) in ss.searcher.NOCASE_ABI.items():
         got = (norm(res), [norm(a) for a in args])
         want = c[name]
