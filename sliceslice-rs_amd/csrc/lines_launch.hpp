@@ -45,9 +45,10 @@ struct CombineArgs {
 };
 
 // The matching-lines scan of one Problem (the kernel choice of launch_scan_all: scan_choice.hpp).  Returns false when no kernel fits.
-bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
+// (`bound`: as for launch_scan_all - 0, ignored)
+bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la, uint32_t bound);
 // (the host side takes the scan as a value of this type: ss_lines.hip, lines_host.hpp)
-typedef bool (*ScanLinesFn)(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la);
+typedef bool (*ScanLinesFn)(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la, uint32_t bound);
 // ceil((end - begin) / part_bytes) workgroups (at least one: an empty range leaves an empty summary)
 hipError_t launch_lines_plain(const PlainArgs &pa, bool every, hipStream_t st);
 // The summaries of `n` parts in chunks of kLineChunk: csum[chunk] = the chunk's summary (spread == false), or - behind the combine

@@ -4,13 +4,16 @@
 // A macro and not a __device__ function that both kernels call: compiled through a function, lines_scan_kernel<0, 0, true> came out
 // with one more spilled scalar register than it has (the body is optimised once as a function before it is inlined); expanded in
 // place the kernel is token for token what it was.
+//
+// SS_LINES_SCAN_KERNEL_AS is the text; BOUND, BOUND_PARAM and BOUND_VALUE are scan_tiles' neighbour test, the kernel argument that
+// carries its wave-uniform mode word and that argument's name (bounded_kernels.hpp) - off, empty and 0 for SS_LINES_SCAN_KERNEL.
 #pragma once
 #include "lines_launch.hpp"
 
 // Contiguous tiles per workgroup (1 <= tiles_per_block <= kLineTilesPerBlock), so that workgroup order is address order.
-#define SS_LINES_SCAN_KERNEL(NAME, FOLD)                                                                                                       \
+#define SS_LINES_SCAN_KERNEL_AS(NAME, FOLD, BOUND, BOUND_PARAM, BOUND_VALUE)                                                                   \
 template <int Q, int MODE, bool ONE_BYTE>                                                                                                      \
-__global__ void __launch_bounds__(kMaxBlock) NAME(const Problem pr, LineArgs la, uint64_t tiles_per_block)                                     \
+__global__ void __launch_bounds__(kMaxBlock) NAME(const Problem pr, LineArgs la, uint64_t tiles_per_block BOUND_PARAM)                         \
 {                                                                                                                                              \
     extern __shared__ __attribute__((aligned(16))) uint8_t s_needle[];                                                                         \
     __shared__ uint64_t s_last[kLineTilesPerBlock * kMaxWavesPerBlock];                                                                        \
@@ -50,7 +53,8 @@ __global__ void __launch_bounds__(kMaxBlock) NAME(const Problem pr, LineArgs la,
         const uint32_t closes = (uint32_t)__builtin_amdgcn_readfirstlane((int)p->closes);                                                      \
         if (closes == 0 || lt.at.rank >= la.capacity) return;                                                                                  \
     }                                                                                                                                          \
-    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, true, FOLD>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &lt);  \
+    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, true, FOLD, BOUND>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &lt,\
+                                                                                                     nullptr, BOUND_VALUE);                    \
     if (la.mode == kLinesEmit) return;                                                                                                         \
     const uint32_t wn = wave_sum(lt.lane_ndelim), wc = wave_sum(lt.lane_closed);                                                               \
     if (lane == 0) {                                                                                                                           \
@@ -91,3 +95,5 @@ __global__ void __launch_bounds__(kMaxBlock) NAME(const Problem pr, LineArgs la,
         la.sum[la.part0 + blockIdx.x] = sum;                                                                                                   \
     }                                                                                                                                          \
 }
+// the two scans without the neighbour test: no further kernel argument
+#define SS_LINES_SCAN_KERNEL(NAME, FOLD) SS_LINES_SCAN_KERNEL_AS(NAME, FOLD, false, , 0u)

@@ -24,10 +24,12 @@ int plan_static(const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t l
 // what every call checks first: the handle, the result pointer, the haystack
 int check_common_args(const ss_searcher *s, const void *d_haystack, size_t len, const void *out);
 
-int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count);
+// (`bound`: handed to `scan` as it is - the whole-word scans' mode word, ss_bounded.hip; 0 for every other scan)
+int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count,
+                      uint32_t bound = 0);
 int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
-                            uint64_t *d_count);
+                            uint64_t *d_count, uint32_t bound = 0);
 int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
-                         uint64_t *d_offsets, uint64_t capacity, uint64_t *count);
+                         uint64_t *d_offsets, uint64_t capacity, uint64_t *count, uint32_t bound = 0);
 
 }  // namespace ssh

@@ -20,7 +20,7 @@ __global__ void store_u64_kernel(uint64_t *out, uint64_t v) { *out = v; }
 
 }  // namespace
 
-bool launch_scan_all(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa)
+bool launch_scan_all(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa, uint32_t)
 {
     return choose_scan_kernel(q, mode, one_byte, [&](auto Q, auto MODE, auto ONE_BYTE) {
         scan_all_kernel<decltype(Q)::value, decltype(MODE)::value, decltype(ONE_BYTE)::value>

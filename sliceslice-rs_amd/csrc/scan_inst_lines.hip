@@ -6,7 +6,7 @@
 
 namespace ss {
 
-bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la)
+bool launch_scan_lines(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la, uint32_t)
 {
     return choose_scan_kernel(q, mode, one_byte, [&](auto Q, auto MODE, auto ONE_BYTE) {
         lines_scan_kernel<decltype(Q)::value, decltype(MODE)::value, decltype(ONE_BYTE)::value>

@@ -7,7 +7,7 @@
 
 namespace ss {
 
-bool launch_scan_all_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa)
+bool launch_scan_all_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const AllArgs &aa, uint32_t)
 {
     return choose_scan_kernel(q, mode, one_byte, [&](auto Q, auto MODE, auto ONE_BYTE) {
         scan_all_nocase_kernel<decltype(Q)::value, decltype(MODE)::value, decltype(ONE_BYTE)::value>
@@ -15,7 +15,7 @@ bool launch_scan_all_nocase(const Problem &pr, int q, int mode, bool one_byte, c
     });
 }
 
-bool launch_scan_lines_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la)
+bool launch_scan_lines_nocase(const Problem &pr, int q, int mode, bool one_byte, const Shape &sh, hipStream_t st, const LineArgs &la, uint32_t)
 {
     return choose_scan_kernel(q, mode, one_byte, [&](auto Q, auto MODE, auto ONE_BYTE) {
         lines_scan_nocase_kernel<decltype(Q)::value, decltype(MODE)::value, decltype(ONE_BYTE)::value>

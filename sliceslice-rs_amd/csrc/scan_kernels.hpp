@@ -79,6 +79,9 @@ template <bool BATCHED> constexpr bool kNoForget = BATCHED;
 // problem counts it into the plan's tally.
 template <class T, class = void> struct SingleLaunchPlan : std::false_type {};
 template <class T> struct SingleLaunchPlan<T, std::void_t<decltype(T::kSingleLaunchPlan)>> : std::bool_constant<T::kSingleLaunchPlan> {};
+// (bounded_kernels.hpp: the occurrences of a lane's match mask whose two neighbour bytes `bound` allows; scan_tiles<..., BOUND = true>)
+__device__ __forceinline__ uint32_t bounded_matches(uint32_t mk, uint64_t i0, const VerifyArgs &va, uint32_t bound);
+
 // ALL (scan_all_kernel only): every match, no early exit.  `sink` is the launch's AllTiles.  There are no flag polls; every candidate of
 // every piece is verified (verify_flags_all / exact_verify_piece_all return a lane's full match mask), and each matching offset belongs
 // to exactly one (wave, piece, lane) - pieces do not overlap, and the exact compare hands a flag to ONE neighbour.  Count launches add
@@ -94,14 +97,15 @@ struct AllTiles {
 };
 
 template <int Q, int MODE, bool ONE_BYTE, int U, int NTMODE, bool FIND = false, bool L8 = false, bool LAZY_ORDER = false,
-          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false, bool FOLD = false>
+          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false, bool FOLD = false, bool BOUND = false>
 __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_t *s_needle_block, uint64_t tile0,
-                                           uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr)
+                                           uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr, uint32_t bound = 0)
 {
     static_assert(!L8 || (MODE == 0 && !FIND), "the 8-byte layout covers the single-stream bool kernels");
     static_assert(!ALL || (!FIND && !L8 && !LAZY_ORDER), "the all-matches mode has kernels of its own (scan_all_kernel)");
     static_assert(!LINES || ALL, "the matching-lines mode (lines_scan_kernel, lines_tiles.hpp) is built on the all-matches one");
     static_assert(!FOLD || ALL, "case folding (nocase_kernels.hpp) exists for the all-matches and matching-lines modes");
+    static_assert(!BOUND || ALL, "the neighbour test (bounded_kernels.hpp) exists for the all-matches and matching-lines modes");
     static_assert(Q != kQDynamic || (MODE == 0 && !L8), "a run-time window is for the single-stream kernels' three-byte phase");
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "single-stream kernels only");
     constexpr bool SHIFTED = MODE >= 2;
@@ -148,6 +152,8 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     // phases, the cross-lane path and the exact compare then work on folded bytes as they are - and whatever reads haystack bytes
     // from memory folds them there.  The delimiter is NOT folded: its masks are taken from the raw registers, before the fold, and
     // a delimiter that is an upper-case letter stays what it is in the folded registers too (keepx4: no occurrence runs across it).
+    // BOUND (the bounded kernels only): a lane's match mask goes through bounded_matches right where it is produced - `bound`
+    // (wave-uniform, a kernel argument) says which neighbour bytes an occurrence may have; what consumes the mask does not change.
     AllTiles *all = static_cast<AllTiles *>(sink);
     LineTiles *lines = static_cast<LineTiles *>(sink);
     uint32_t all_mask[U];
@@ -621,6 +627,10 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
                         const uint64_t far_off = MODE == 0 && !ONE_BYTE ? uniform64(cold()->far_off) : 0;
                         mk = verify_flags_all<ONE_BYTE, FOLD>(g, chunk0 + 64 * u + lane, pr, va, s_needle, far_off, keepx4);
                     }
+                    if constexpr (BOUND) {
+                        // (both masks: bit t is the occurrence at hay index (chunk0 + 64 u + lane) * 16 - mis + t, t < 32)
+                        if (mk != 0) mk = bounded_matches(mk, (chunk0 + 64 * u + lane) * 16 - pr.mis, va, bound);
+                    }
                     if constexpr (LINES) {
                         all_mask[u] = mk;
                     } else {
@@ -873,8 +883,9 @@ constexpr uint32_t kAllCount = 0, kAllCountPerWorkgroup = 1, kAllEmit = 2;
 
 // Contiguous tiles per workgroup (tiles_per_block >= 1), so that workgroup order is address order.  No entry peek, no flag poll.
 // (the kernel's body, shared with its case-folding twin - nocase_kernels.hpp; `pr` is the kernel's first argument)
-template <int Q, int MODE, bool ONE_BYTE, bool FOLD>
-__device__ __forceinline__ void scan_all_body(const Problem &pr, const AllArgs &aa, uint64_t tiles_per_block)
+// (BOUND, `bound`: the bounded kernels' neighbour test - bounded_kernels.hpp)
+template <int Q, int MODE, bool ONE_BYTE, bool FOLD, bool BOUND = false>
+__device__ __forceinline__ void scan_all_body(const Problem &pr, const AllArgs &aa, uint64_t tiles_per_block, uint32_t bound = 0)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_needle[];
     __shared__ uint32_t s_wave[kMaxWavesPerBlock];
@@ -894,7 +905,8 @@ __device__ __forceinline__ void scan_all_body(const Problem &pr, const AllArgs &
         if (cnt == 0 || rank >= aa.capacity) return;
         at.rank = rank;
     }
-    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, false, FOLD>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &at);
+    scan_tiles<Q, MODE, ONE_BYTE, U, 1, false, false, false, ColdInKernarg, true, false, FOLD, BOUND>(pr, ColdInKernarg{}, s_needle, t0, 1, t1, &at,
+                                                                                                      nullptr, bound);
     if (aa.mode == kAllEmit) return;
     const uint32_t wc = wave_sum(at.lane_count);
     if (lane == 0) s_wave[wave] = wc;

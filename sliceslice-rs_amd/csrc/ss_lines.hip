@@ -99,7 +99,7 @@ int combine_parts(const LinesScratch &sc, size_t len, const LinesOut &o, bool em
 // Enqueues everything; *d_total = the scratch word that takes the total.  Preconditions: len >= 1, the needle holds no delimiter,
 // n <= len.
 int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, int delimiter, hipStream_t st, const LinesOut &o,
-                  ScratchLease *lease, uint64_t **d_total)
+                  ScratchLease *lease, uint64_t **d_total, uint32_t bound)
 {
     const uint8_t *hay = static_cast<const uint8_t *>(d_hay);
     const bool emit = o.capacity != 0 && (o.begin || o.end || o.number);
@@ -138,13 +138,13 @@ int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, con
     HIP_TRY(ss::launch_lines_plain(head, false, st));
     HIP_TRY(ss::launch_lines_plain(tail, false, st));
     ss::LineArgs la = {sum, pre, o.begin, o.end, o.number, o.capacity, ll.dlo, ll.dhi, ll.hshift, 1, (uint32_t)delimiter, ss::kLinesSum};
-    if (!scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la))
+    if (!scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la, bound))
         return fail(SS_ERR_ARGUMENT, "no lines kernel for mode %d, window %d", ll.mode, ll.q);
     HIP_TRY(hipGetLastError());
     if (int rc = combine_parts(sc, len, o, emit, st)) return rc;
     if (emit) {
         la.mode = ss::kLinesEmit;
-        (void)scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la);
+        (void)scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la, bound);
         HIP_TRY(hipGetLastError());
         if (ll.tail_begin < len) {              // (the head has nothing in front of it that could be pending)
             tail.mode = ss::kLinesEmit;
@@ -169,7 +169,7 @@ bool no_line(const ss_searcher *s, size_t len, int delimiter)
 }
 
 int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, const LinesOut &o,
-                   uint64_t *lines)
+                   uint64_t *lines, uint32_t bound)
 {
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
     if (no_line(s, len, delimiter)) { *lines = 0; return SS_OK; }
@@ -178,7 +178,7 @@ int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_hay
     if (int rc = get_per_device(s, &pd)) return rc;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound)) return rc;
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
@@ -190,14 +190,14 @@ int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_hay
 
 // (lines_host.hpp: `scan` is launch_scan_lines, or its case-folding twin for ss_nocase.hip)
 int count_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
-                            void *hip_stream, uint64_t *lines)
+                            void *hip_stream, uint64_t *lines, uint32_t bound)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
-    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines, bound);
 }
 
 int count_lines_device_async_with(ss::ScanLinesFn scan, const char *name, const ss_searcher *s, const void *d_haystack, size_t len,
-                                  int delimiter, void *hip_stream, uint64_t *d_lines)
+                                  int delimiter, void *hip_stream, uint64_t *d_lines, uint32_t bound)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, d_lines)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -215,12 +215,13 @@ int count_lines_device_async_with(ss::ScanLinesFn scan, const char *name, const 
     o.d_total2 = d_lines;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound)) return rc;
     return lease.release_on(st);
 }
 
 int find_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
-                           void *hip_stream, uint64_t *d_begin, uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines)
+                           void *hip_stream, uint64_t *d_begin, uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines,
+                           uint32_t bound)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
     LinesOut o;
@@ -228,7 +229,7 @@ int find_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const voi
     o.end = d_end;
     o.number = d_number;
     o.capacity = capacity;
-    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, o, lines);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, o, lines, bound);
 }
 
 }  // namespace ssh

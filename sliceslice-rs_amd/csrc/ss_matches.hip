@@ -44,9 +44,9 @@ namespace {
 
 // (the call-owned scratch - Scratch, take_scratch, ScratchLease: matches_scratch.hpp, shared with ss_matches_batched.hip)
 
-int launch_all(ss::ScanAllFn scan, const StaticPlan &al, hipStream_t st, const ss::AllArgs &aa)
+int launch_all(ss::ScanAllFn scan, const StaticPlan &al, hipStream_t st, const ss::AllArgs &aa, uint32_t bound)
 {
-    if (!scan(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa))
+    if (!scan(al.pr, al.q, al.mode, al.one_byte, al.shape, st, aa, bound))
         return fail(SS_ERR_ARGUMENT, "no all-matches kernel for mode %d, window %d", al.mode, al.q);
     HIP_TRY(hipGetLastError());
     return SS_OK;
@@ -54,9 +54,9 @@ int launch_all(ss::ScanAllFn scan, const StaticPlan &al, hipStream_t st, const s
 
 }  // namespace
 
-// (matches_host.hpp: `scan` is launch_scan_all, or its case-folding twin for ss_nocase.hip)
+// (matches_host.hpp: `scan` is launch_scan_all, its case-folding twin for ss_nocase.hip, or a whole-word scan with its `bound`)
 int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
-                            uint64_t *d_count)
+                            uint64_t *d_count, uint32_t bound)
 {
     if (int rc = check_common_args(s, d_haystack, len, d_count)) return rc;
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
@@ -73,10 +73,11 @@ int count_device_async_with(ss::ScanAllFn scan, const ss_searcher *s, const void
     StaticPlan al;
     if (int rc = plan_static(s, pd, d_haystack, len, &al)) return rc;
     const ss::AllArgs aa = {d_count, nullptr, nullptr, nullptr, 0, ss::kAllCount};
-    return launch_all(scan, al, st, aa);
+    return launch_all(scan, al, st, aa, bound);
 }
 
-int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count)
+int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream, uint64_t *count,
+                      uint32_t bound)
 {
     if (int rc = check_common_args(s, d_haystack, len, count)) return rc;
     SearchGate gate(s);
@@ -92,7 +93,7 @@ int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_ha
     uint64_t *d_total = reinterpret_cast<uint64_t *>(lease.sc.d);
     HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(uint64_t), st));
     const ss::AllArgs aa = {d_total, nullptr, nullptr, nullptr, 0, ss::kAllCount};
-    if (int rc = launch_all(scan, al, st, aa)) return rc;
+    if (int rc = launch_all(scan, al, st, aa, bound)) return rc;
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
@@ -101,7 +102,7 @@ int count_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_ha
 }
 
 int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d_haystack, size_t len, void *hip_stream,
-                         uint64_t *d_offsets, uint64_t capacity, uint64_t *count)
+                         uint64_t *d_offsets, uint64_t capacity, uint64_t *count, uint32_t bound)
 {
     if (int rc = check_common_args(s, d_haystack, len, count)) return rc;
     if (capacity && !d_offsets) return fail(SS_ERR_ARGUMENT, "offsets are NULL with a capacity of %llu", (unsigned long long)capacity);
@@ -129,11 +130,11 @@ int find_all_device_with(ss::ScanAllFn scan, const ss_searcher *s, const void *d
     uint64_t *d_rank = d_total + 1;
     uint32_t *d_wg = reinterpret_cast<uint32_t *>(d_rank + blocks);
     const ss::AllArgs counting = {nullptr, d_wg, nullptr, nullptr, 0, ss::kAllCountPerWorkgroup};
-    if (int rc = launch_all(scan, al, st, counting)) return rc;
+    if (int rc = launch_all(scan, al, st, counting, bound)) return rc;
     HIP_TRY(ss::launch_prefix(d_wg, blocks, d_rank, d_total, st));
     if (capacity) {
         const ss::AllArgs emitting = {nullptr, d_wg, d_rank, d_offsets, capacity, ss::kAllEmit};
-        if (int rc = launch_all(scan, al, st, emitting)) return rc;
+        if (int rc = launch_all(scan, al, st, emitting, bound)) return rc;
     }
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

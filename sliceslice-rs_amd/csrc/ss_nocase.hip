@@ -20,7 +20,9 @@ namespace {
 
 inline bool is_upper(uint8_t b) { return b >= 'A' && b <= 'Z'; }
 
-// the kernels compare folded haystack bytes with the needle's bytes as they are
+}  // namespace
+
+// the kernels compare folded haystack bytes with the needle's bytes as they are (nocase_launch.hpp: ss_bounded.hip asks too)
 int check_folded(const ss_searcher *s, const char *name)
 {
     if (!s) return SS_OK;                           // (the models' argument checks name it)
@@ -31,7 +33,6 @@ int check_folded(const ss_searcher *s, const char *name)
                                  "(or from a needle without 'A'..'Z')", name, (unsigned)*up, (size_t)(up - s->needle.begin()));
 }
 
-}  // namespace
 }  // namespace ssh
 
 using namespace ssh;

@@ -127,6 +127,18 @@ NOCASE_ABI = {
     "ss_count_lines_nocase_device_async": (_int, [_vp, _vp, _sz, _int, _vp, _vp]),
     "ss_find_lines_nocase_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_bounded.h: whole-word / whole-line occurrences and matching lines - libsliceslice_hip_bounded.so only (the
+# nocase library's objects plus the bounded scans); the models' argument lists with `unsigned how` in front of the stream
+_uint = ctypes.c_uint
+BOUNDED_ABI = {
+    "ss_count_bounded_device": (_int, [_vp, _vp, _sz, _uint, _vp, _pu64]),
+    "ss_count_bounded_device_async": (_int, [_vp, _vp, _sz, _uint, _vp, _vp]),
+    "ss_find_all_bounded_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_bounded_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _pu64]),
+    "ss_count_lines_bounded_device_async": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp]),
+    "ss_find_lines_bounded_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
+SS_BOUND_WORD, SS_BOUND_LINE, SS_BOUND_NOCASE = 1, 2, 4
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -218,7 +230,8 @@ def _bind(L, table, strict):
 
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
-# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES under their names, and the test hooks.
+# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES and _build.MORE_LIBRARIES under their names,
+# and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -239,6 +252,9 @@ _FEATURES = {
     "nocase": (NOCASE_ABI, "ss_count_nocase_device",
                "ignore_case=True / new_nocase are not part of this library: they live in "
                "libsliceslice_hip_nocase.so - create the searcher inside `with ss.nocase_build():`"),
+    "bounded": (BOUNDED_ABI, "ss_count_bounded_device",
+                "whole_word=True / whole_line=True are not part of this library: they live in "
+                "libsliceslice_hip_bounded.so - create the searcher inside `with ss.bounded_build():`"),
 }
 
 
@@ -284,8 +300,8 @@ def tools_lib():
 
 
 class _library_build:
-    """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES, or
-    "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES or
+    _build.MORE_LIBRARIES, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -339,6 +355,13 @@ class nocase_build(_library_build):
     name = "nocase"
 
 
+class bounded_build(_library_build):
+    """libsliceslice_hip_bounded.so: the nocase library plus the whole-word / whole-line forms (include/sliceslice_hip_bounded.h:
+    ``whole_word=True`` on ``count`` / ``find_all`` / ``count_lines`` / ``find_lines`` and ``whole_line=True`` on the two line
+    methods of searchers created inside the block; both combine with ``ignore_case=True``)."""
+    name = "bounded"
+
+
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
 
 
@@ -346,6 +369,13 @@ def fold_ascii(data):
     """``data`` with the bytes 'A'..'Z' replaced by 'a'..'z' and every other byte value as it is - the fold of the calls that
     ignore ASCII case (``bytes.lower()``)."""
     return bytes(data).translate(_FOLD_TABLE)
+
+
+def is_word_byte(b):
+    """True for the word bytes of the whole-word forms (include/sliceslice_hip_bounded.h): '0'..'9', 'A'..'Z', 'a'..'z' and '_' -
+    ``grep -w`` in the C locale.  No byte >= 0x80 is one."""
+    b = int(b)
+    return 0x30 <= b <= 0x39 or 0x41 <= b <= 0x5A or 0x61 <= b <= 0x7A or b == 0x5F
 
 
 def _delimiter_byte(delimiter):
@@ -357,9 +387,16 @@ def _delimiter_byte(delimiter):
     return int(delimiter)
 
 
-def _scan_fn(L, name, ignore_case):
+def _scan_fn(L, name, ignore_case, whole_word=False, whole_line=False):
     """The function `name` of the matches or the lines library from `L`, or - ignore_case - its folding form from the nocase
-    library: ss_count_device -> ss_count_nocase_device, ss_find_lines_device -> ss_find_lines_nocase_device, ..."""
+    library: ss_count_device -> ss_count_nocase_device, ss_find_lines_device -> ss_find_lines_nocase_device, ...
+    whole_word / whole_line: its form in the bounded library (ss_count_bounded_device, ...) behind the SAME argument list - `how`
+    (SS_BOUND_WORD / SS_BOUND_LINE, | SS_BOUND_NOCASE with ignore_case) goes in front of the stream here."""
+    if whole_word or whole_line:
+        fn = getattr(_feature_lib(L, "bounded"), name.replace("_device", "_bounded_device"))
+        how = (SS_BOUND_WORD if whole_word else 0) | (SS_BOUND_LINE if whole_line else 0) | (SS_BOUND_NOCASE if ignore_case else 0)
+        at = 4 if "_lines_" in name else 3                  # (searcher, haystack, len[, delimiter], HOW, stream, ...)
+        return lambda *a: fn(*a[:at], how, *a[at:])
     if ignore_case:
         return getattr(_feature_lib(L, "nocase"), name.replace("_device", "_nocase_device"))
     return getattr(_feature_lib(L, "lines" if "_lines_" in name else "matches"), name)
@@ -538,11 +575,14 @@ class DynamicHipSearcher:
             raise TypeError("device haystack must be a contiguous 1-byte tensor")
         return haystack.data_ptr(), haystack.numel(), haystack
 
-    def count(self, haystack, stream=None, ignore_case=False):
+    def count(self, haystack, stream=None, ignore_case=False, whole_word=False):
         """int: the number of (overlapping) occurrences of the needle in ``haystack`` (ss_count_device).  Empty needle: len + 1.
         ignore_case=True (here and in the seven methods below; searchers made inside ``with ss.nocase_build():`` from a needle
-        without upper-case bytes - ``new_nocase`` folds one): haystack letters match in either case (ss_count_nocase_device)."""
-        fn = _scan_fn(self._L, "ss_count_device", ignore_case)
+        without upper-case bytes - ``new_nocase`` folds one): haystack letters match in either case (ss_count_nocase_device).
+        whole_word=True (likewise; searchers made inside ``with ss.bounded_build():``, a non-empty needle): only occurrences whose
+        two neighbour bytes are absent or no word bytes (``is_word_byte``) - ``grep -w`` (ss_count_bounded_device).  The four line
+        methods also take a delimiter for a neighbour, and whole_line=True (``grep -x``): neighbours absent or the delimiter."""
+        fn = _scan_fn(self._L, "ss_count_device", ignore_case, whole_word)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
@@ -550,18 +590,18 @@ class DynamicHipSearcher:
             self._ck(fn(self._h, ptr, length, st, ctypes.byref(c)))
         return c.value
 
-    def count_async(self, haystack, d_count, stream=None, ignore_case=False):
+    def count_async(self, haystack, d_count, stream=None, ignore_case=False, whole_word=False):
         """Enqueue only (ss_count_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        fn = _scan_fn(self._L, "ss_count_device_async", ignore_case)
+        fn = _scan_fn(self._L, "ss_count_device_async", ignore_case, whole_word)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
             self._ck(fn(self._h, haystack.data_ptr(), haystack.numel(), st, d_count.data_ptr()))
 
-    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False):
+    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False, whole_word=False):
         """int64 tensor on the haystack's device: the offsets of every (overlapping) occurrence in ascending order
         (ss_find_all_device).  capacity=None: counted first, then exactly that many; else the leftmost ``capacity`` of them."""
         import torch
-        count_fn, find_fn = _scan_fn(self._L, "ss_count_device", ignore_case), _scan_fn(self._L, "ss_find_all_device", ignore_case)
+        count_fn, find_fn = _scan_fn(self._L, "ss_count_device", ignore_case, whole_word), _scan_fn(self._L, "ss_find_all_device", ignore_case, whole_word)
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         total = _u64(0)
@@ -575,9 +615,9 @@ class DynamicHipSearcher:
                              ctypes.byref(total)))
         return out[:min(int(capacity), total.value)]
 
-    def find_all_into(self, haystack, d_offsets, stream=None, ignore_case=False):
+    def find_all_into(self, haystack, d_offsets, stream=None, ignore_case=False, whole_word=False):
         """ss_find_all_device into a caller's 8-byte device tensor (capacity = its length); returns the total count."""
-        fn = _scan_fn(self._L, "ss_find_all_device", ignore_case)
+        fn = _scan_fn(self._L, "ss_find_all_device", ignore_case, whole_word)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
@@ -586,11 +626,11 @@ class DynamicHipSearcher:
         return total.value
 
     # -- the lines that contain the needle (libsliceslice_hip_lines.so: searchers made inside `with ss.lines_build():`) ------
-    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False):
+    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """int: the number of lines of ``haystack`` (cut at every ``delimiter`` byte) that hold at least one occurrence of the
         needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines.  ignore_case=True folds the
         haystack's letters, never the delimiter."""
-        fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case)
+        fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case, whole_word, whole_line)
         ptr, length, t = self._device_haystack(haystack)
         c = _u64(0)
         with _on_device_of(t):
@@ -598,21 +638,21 @@ class DynamicHipSearcher:
             self._ck(fn(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
         return c.value
 
-    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False):
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """Enqueue only (ss_count_lines_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        fn = _scan_fn(self._L, "ss_count_lines_device_async", ignore_case)
+        fn = _scan_fn(self._L, "ss_count_lines_device_async", ignore_case, whole_word, whole_line)
         with _on_device_of(haystack):
             st = stream if stream is not None else _current_stream_handle()
             self._ck(fn(self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
 
-    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False):
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """(begin, end, number): three int64 tensors on the haystack's device, one entry per matching line in ascending order - the
         offset of its first byte, the offset of the delimiter that closes it (len for a last line without one) and its 1-based
         line number (ss_find_lines_device).  capacity=None: counted first (ss_count_lines_device: one more pass over the haystack, as
         ``find_all`` does), then exactly that many; with a capacity the haystack is read at most twice and the leftmost ``capacity``
         records come back."""
         import torch
-        count_fn, find_fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case), _scan_fn(self._L, "ss_find_lines_device", ignore_case)
+        count_fn, find_fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case, whole_word, whole_line), _scan_fn(self._L, "ss_find_lines_device", ignore_case, whole_word, whole_line)
         ptr, length, t = self._device_haystack(haystack)
         dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
         d = _delimiter_byte(delimiter)
@@ -628,9 +668,9 @@ class DynamicHipSearcher:
         k = min(int(capacity), total.value)
         return out[0, :k], out[1, :k], out[2, :k]
 
-    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False):
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """ss_find_lines_device into the caller's 8-byte device tensors (each may be None: not wanted); returns the total count."""
-        fn = _scan_fn(self._L, "ss_find_lines_device", ignore_case)
+        fn = _scan_fn(self._L, "ss_find_lines_device", ignore_case, whole_word, whole_line)
         ptr, length, t = self._device_haystack(haystack)
         total = _u64(0)
         with _on_device_of(t):
@@ -758,23 +798,23 @@ class MemchrHipSearcher:
     def find(self, haystack, stream=None):
         return self._inner.find(haystack, stream)
 
-    def count(self, haystack, stream=None, ignore_case=False):
-        return self._inner.count(haystack, stream, ignore_case)
+    def count(self, haystack, stream=None, ignore_case=False, whole_word=False):
+        return self._inner.count(haystack, stream, ignore_case, whole_word)
 
-    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False):
-        return self._inner.find_all(haystack, capacity, stream, ignore_case)
+    def find_all(self, haystack, capacity=None, stream=None, ignore_case=False, whole_word=False):
+        return self._inner.find_all(haystack, capacity, stream, ignore_case, whole_word)
 
-    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False):
-        return self._inner.count_lines(haystack, delimiter, stream, ignore_case)
+    def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.count_lines(haystack, delimiter, stream, ignore_case, whole_word, whole_line)
 
-    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False):
-        return self._inner.count_lines_async(haystack, d_count, delimiter, stream, ignore_case)
+    def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.count_lines_async(haystack, d_count, delimiter, stream, ignore_case, whole_word, whole_line)
 
-    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False):
-        return self._inner.find_lines(haystack, delimiter, capacity, stream, ignore_case)
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.find_lines(haystack, delimiter, capacity, stream, ignore_case, whole_word, whole_line)
 
-    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False):
-        return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case)
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
 
 
 def shard_range(length, needle_len, nranks, rank):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""./grep_hip.py [-i] <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
+"""./grep_hip.py [-i] [-w | -x] <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
 "hip" backend: map the file, build one searcher, one search_in, print the boolean.
   --count        the number of (overlapping) OCCURRENCES, not lines (libsliceslice_hip_matches.so, ss_count_device)
   --offsets      grep -b -o style: one byte offset per occurrence, ascending (ss_find_all_device)
@@ -8,9 +8,14 @@
                  bytes of those lines travel to the host)
   -i, --ignore-case  with one of the four switches above: ASCII letters match in either case, every other byte exactly (grep -i
                  in the C locale; libsliceslice_hip_nocase.so, the ss_*_nocase_device calls).  The line delimiter is not folded.
+  -w, --word-regexp  with one of the four switches: only occurrences that stand as whole words - both neighbour bytes absent, the
+                 line's end (line outputs) or outside [0-9A-Za-z_] (grep -w in the C locale; libsliceslice_hip_bounded.so, the
+                 ss_*_bounded_device calls).  Combines with -i.  The empty needle is refused.
+  -x, --line-regexp  with --count-lines or --lines: only lines that ARE the needle (grep -x).  Combines with -i, not with -w; with
+                 the occurrence outputs it is an error.
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
 per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched).  The batched
-library has no case-folding form: -i with -e / -f is refused."""
+library has no case-folding and no whole-word form: -i, -w and -x with -e / -f are refused."""
 import os
 import sys
 
@@ -33,11 +38,11 @@ def count_patterns(patterns, filename):
         return counts.cpu().tolist()
 
 
-def matching_lines(searcher, data, ignore_case=False):
+def matching_lines(searcher, data, ignore_case=False, **bound):
     """[(number, line bytes)] of the lines that contain the needle: the records, then only those byte ranges, come to the host."""
     import torch
     hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
-    begin, end, number = searcher.find_lines(hay, ignore_case=ignore_case)
+    begin, end, number = searcher.find_lines(hay, ignore_case=ignore_case, **bound)
     if begin.numel() == 0:
         return []
     # gather the matching lines' bytes on the device: one copy of sum(end - begin) bytes instead of the whole file
@@ -63,10 +68,15 @@ def main():
         else:
             argv.append(a)
     fold = "-i" in argv or "--ignore-case" in argv
-    argv = [a for a in argv if a not in ("-i", "--ignore-case")]
+    word = "-w" in argv or "--word-regexp" in argv
+    line = "-x" in argv or "--line-regexp" in argv
+    argv = [a for a in argv if a not in ("-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp")]
     args = [a for a in argv if not a.startswith("--")]
     flags = {a for a in argv if a.startswith("--")}
     if patterns:
+        if word or line:
+            raise SystemExit("./grep_hip.py: -w / -x are not available with -e / -f: several patterns go through the batched library, "
+                             "which has no whole-word form - run one pattern per call")
         if fold:
             raise SystemExit("./grep_hip.py: -i is not available with -e / -f: several patterns go through the batched library, "
                              "which has no case-folding form - run one pattern per call")
@@ -75,8 +85,33 @@ def main():
         sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
         return
     if len(args) < 2 or flags - {"--count", "--offsets", "--count-lines", "--lines", "--rare-position"}:
-        raise SystemExit("./grep_hip.py [-i | --ignore-case] <needle> <file> [--count | --offsets | --count-lines | --lines]")
+        raise SystemExit("./grep_hip.py [-i | --ignore-case] [-w | --word-regexp | -x | --line-regexp] <needle> <file> "
+                         "[--count | --offsets | --count-lines | --lines]")
     needle, filename = args[0].encode(), args[1]
+    if word or line:
+        if word and line:
+            raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
+        if not flags & {"--count", "--offsets", "--count-lines", "--lines"}:
+            raise SystemExit("./grep_hip.py: -w / -x need one of --count, --offsets, --count-lines, --lines (the early-exit search has "
+                             "no whole-word form)")
+        if line and not flags & {"--count-lines", "--lines"}:
+            raise SystemExit("./grep_hip.py: -x is about lines: it goes with --count-lines or --lines, not with the occurrence outputs")
+        if not needle:
+            raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
+        bound = dict(whole_word=word, whole_line=line) if flags & {"--count-lines", "--lines"} else dict(whole_word=word)
+        with ss.bounded_build():
+            searcher = ss.DynamicHipSearcher.new_nocase(needle) if fold else ss.DynamicHipSearcher.new(needle)
+        data = open(filename, "rb").read()
+        if "--lines" in flags:
+            for n, text in matching_lines(searcher, data, ignore_case=fold, **bound):
+                sys.stdout.buffer.write(b"%d:%s\n" % (n, text))
+        elif "--count-lines" in flags:
+            print(searcher.count_lines(data, ignore_case=fold, **bound))
+        elif "--offsets" in flags:
+            sys.stdout.write("".join("%d\n" % o for o in searcher.find_all(data, ignore_case=fold, **bound).cpu().tolist()))
+        else:
+            print(searcher.count(data, ignore_case=fold, **bound))
+        return
     if fold:
         if not flags & {"--count", "--offsets", "--count-lines", "--lines"}:
             raise SystemExit("./grep_hip.py: -i needs one of --count, --offsets, --count-lines, --lines (the early-exit search has no "
