@@ -223,16 +223,20 @@ __device__ __forceinline__ uint32_t line_wave_summary(const LineTiles &lt, const
 }
 
 // The records of a wave's part of a tile, `s` = the state in front of it (wave-uniform).
-template <int U>
+// INVERT (the inverted emit kernels only, inverted_kernels.hpp): the delimiters that close a line WITHOUT a match are the selected
+// ones - the complement of line_piece's within the delimiters - and a record's rank is the number of such lines in front of it,
+// delimiters - matching lines, for the state, the lane prefix sums and the wave totals alike.  `s` arrives as the model's state.
+template <int U, bool INVERT = false>
 __device__ __forceinline__ void line_wave_emit(const LineTiles &lt, const uint32_t (&dmT)[U], const uint32_t (&mk)[U], uint64_t chunk0,
                                                int lane, LinePre s)
 {
     uint32_t c = s.carry;
+    if constexpr (INVERT) s.rank = s.ndelim - s.rank;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const uint32_t dm = line_ordered(dmT[u]), mm = line_matches(mk[u], lane);
         uint64_t HD;
-        const uint32_t cm = line_piece(dm, mm, c, lane, HD);
+        const uint32_t cm = INVERT ? dm & ~line_piece(dm, mm, c, lane, HD) : line_piece(dm, mm, c, lane, HD);
         if (HD == 0) continue;                                                   // (nothing closes without a delimiter)
         const uint32_t ndl = (uint32_t)__builtin_popcount(dm), ncl = (uint32_t)__builtin_popcount(cm);
         const uint32_t ex_nd = wave_exclusive_sum(ndl, lane), ex_cl = wave_exclusive_sum(ncl, lane);
@@ -265,13 +269,14 @@ __device__ __forceinline__ void line_wave_emit(const LineTiles &lt, const uint32
     }
 }
 
-// End of a tile in a lines launch (scan_tiles' tile_done).
-template <int U>
+// End of a tile in a lines launch (scan_tiles' tile_done).  INVERT: an emit-only launch (lt.emit is not looked at, so that the
+// summing half compiles away) whose waves write the lines they close that hold no match.
+template <int U, bool INVERT = false>
 __device__ __forceinline__ void line_tile_done(LineTiles &lt, const uint32_t (&dmT)[U], const uint32_t (&mk)[U], uint64_t tile,
                                                uint64_t chunk0, int lane, int wave, int wpb)
 {
     uint64_t last;
-    if (!lt.emit) {
+    if (!INVERT && !lt.emit) {
         const uint32_t flags = line_wave_summary<U>(lt, dmT, mk, chunk0, lane, last, lt.lane_ndelim, lt.lane_closed);
         if (lane == 0) {
             const uint32_t slot = (uint32_t)(tile - lt.tile0) * kMaxWavesPerBlock + (uint32_t)wave;
@@ -301,7 +306,13 @@ __device__ __forceinline__ void line_tile_done(LineTiles &lt, const uint32_t (&d
         (void)line_advance(lt.at, e);
     }
     __syncthreads();                                            // (the next tile rewrites the entries)
-    if (wcl != 0 || (mine.carry && (flags & kLineHas))) line_wave_emit<U>(lt, dmT, mk, chunk0, lane, mine);
+    if constexpr (INVERT) {
+        // wcl holds the first delimiter's line when the wave's own head matches; a match pending in front of the wave makes it one too
+        const uint32_t pending = (mine.carry && (flags & (kLineHas | kLineHead)) == kLineHas) ? 1u : 0u;
+        if (wnd > wcl + pending) line_wave_emit<U, true>(lt, dmT, mk, chunk0, lane, mine);
+    } else {
+        if (wcl != 0 || (mine.carry && (flags & kLineHas))) line_wave_emit<U>(lt, dmT, mk, chunk0, lane, mine);
+    }
 }
 
 }  // namespace ss

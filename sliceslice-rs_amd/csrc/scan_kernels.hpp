@@ -97,7 +97,8 @@ struct AllTiles {
 };
 
 template <int Q, int MODE, bool ONE_BYTE, int U, int NTMODE, bool FIND = false, bool L8 = false, bool LAZY_ORDER = false,
-          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false, bool FOLD = false, bool BOUND = false>
+          typename ColdT = ColdInRegisters, bool ALL = false, bool LINES = false, bool FOLD = false, bool BOUND = false,
+          bool INVERT = false>
 __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_t *s_needle_block, uint64_t tile0,
                                            uint64_t tile_step, uint64_t tile_end, void *sink, void *wg_sink = nullptr, uint32_t bound = 0)
 {
@@ -106,6 +107,7 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     static_assert(!LINES || ALL, "the matching-lines mode (lines_scan_kernel, lines_tiles.hpp) is built on the all-matches one");
     static_assert(!FOLD || ALL, "case folding (nocase_kernels.hpp) exists for the all-matches and matching-lines modes");
     static_assert(!BOUND || ALL, "the neighbour test (bounded_kernels.hpp) exists for the all-matches and matching-lines modes");
+    static_assert(!INVERT || LINES, "the complemented selection (inverted_kernels.hpp) exists for the matching-lines mode's emit launches");
     static_assert(Q != kQDynamic || (MODE == 0 && !L8), "a run-time window is for the single-stream kernels' three-byte phase");
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "single-stream kernels only");
     constexpr bool SHIFTED = MODE >= 2;
@@ -154,6 +156,7 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     // a delimiter that is an upper-case letter stays what it is in the folded registers too (keepx4: no occurrence runs across it).
     // BOUND (the bounded kernels only): a lane's match mask goes through bounded_matches right where it is produced - `bound`
     // (wave-uniform, a kernel argument) says which neighbour bytes an occurrence may have; what consumes the mask does not change.
+    // INVERT (the inverted emit kernels only): line_tile_done writes the lines WITHOUT a match; nothing else changes.
     AllTiles *all = static_cast<AllTiles *>(sink);
     LineTiles *lines = static_cast<LineTiles *>(sink);
     uint32_t all_mask[U];
@@ -162,7 +165,7 @@ __device__ __forceinline__ void scan_tiles(const Problem &pr, ColdT cold, uint8_
     if constexpr (FOLD && LINES) keepx4 = ((lines->delim_x4 & 0xFFu) - 'A') < 26u ? lines->delim_x4 : 0u;       // (wave-uniform)
     auto tile_done = [&](uint64_t tile) {
         if constexpr (LINES) {
-            line_tile_done<U>(*lines, line_dm, all_mask, tile, (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64, lane, wave, wpb);
+            line_tile_done<U, INVERT>(*lines, line_dm, all_mask, tile, (tile * (uint64_t)(wpb * U) + (uint64_t)wave * U) * 64, lane, wave, wpb);
         } else if constexpr (ALL) {
             if (all->emit) {
                 uint32_t c = 0;

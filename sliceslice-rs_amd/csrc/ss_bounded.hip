@@ -3,12 +3,13 @@
 // and scan_inst_bounded_nocase.hip.
 //
 // The host side is the models' own (matches_host.hpp, lines_host.hpp) with the bounded scans of bounded_kernels.hpp in place of
-// launch_scan_all / launch_scan_lines and their mode word as the helpers' last argument.  This file checks `how` and the needle
+// launch_scan_all / launch_scan_lines and their mode word as the helpers' last argument.  check_how (bounded_how.hpp) checks `how` and the needle
 // (not empty; no upper-case byte with SS_BOUND_NOCASE) and builds the mode word; n > len and a needle that holds the delimiter are
 // settled by the models' code before any scan is launched.
 #include "ss_internal.hpp"
 
 #include "../../include/sliceslice_hip_bounded.h"
+#include "bounded_how.hpp"
 #include "bounded_launch.hpp"
 #include "lines_host.hpp"
 #include "matches_host.hpp"
@@ -16,30 +17,6 @@
 
 namespace ssh {
 namespace {
-
-// `how` and the needle of one call -> SS_OK and *bound, or the refusal.  line_form: a delimiter exists (checked by the models' code
-// behind this; an invalid one never reaches a kernel).
-int check_how(const ss_searcher *s, unsigned how, bool line_form, int delimiter, const char *name, uint32_t *bound)
-{
-    const char *plain = line_form ? "ss_count_lines_device / ss_find_lines_device" : "ss_count_device / ss_find_all_device";
-    const char *folding = line_form ? "ss_count_lines_nocase_device / ss_find_lines_nocase_device" : "ss_count_nocase_device / ss_find_all_nocase_device";
-    if (how & ~(SS_BOUND_WORD | SS_BOUND_LINE | SS_BOUND_NOCASE))
-        return fail(SS_ERR_ARGUMENT, "%s: how = 0x%x holds bits other than SS_BOUND_WORD | SS_BOUND_LINE | SS_BOUND_NOCASE", name, how);
-    const bool word = (how & SS_BOUND_WORD) != 0, line = (how & SS_BOUND_LINE) != 0;
-    if (!word && !line)
-        return fail(SS_ERR_ARGUMENT, "%s: how names neither SS_BOUND_WORD nor SS_BOUND_LINE; without a bound the call is %s", name,
-                    (how & SS_BOUND_NOCASE) ? folding : plain);
-    if (word && line)
-        return fail(SS_ERR_ARGUMENT, "%s: how names both SS_BOUND_WORD and SS_BOUND_LINE; a call takes one of them", name);
-    if (line && !line_form)
-        return fail(SS_ERR_ARGUMENT, "%s: SS_BOUND_LINE needs lines; it belongs to ss_count_lines_bounded_device / ss_find_lines_bounded_device", name);
-    if (s && s->n == 0)
-        return fail(SS_ERR_ARGUMENT, "%s: the empty needle has no neighbour bytes to test (it is out of scope here)", name);
-    if (how & SS_BOUND_NOCASE)
-        if (int rc = check_folded(s, name)) return rc;
-    *bound = (word ? ss::kBoundWord : 0u) | (line_form ? ss::kBoundDelim | ((uint32_t)(delimiter & 0xFF) << ss::kBoundDelimShift) : 0u);
-    return SS_OK;
-}
 
 ss::ScanAllFn scan_all_of(unsigned how) { return (how & SS_BOUND_NOCASE) ? ss::launch_scan_all_bounded_nocase : ss::launch_scan_all_bounded; }
 ss::ScanLinesFn scan_lines_of(unsigned how) { return (how & SS_BOUND_NOCASE) ? ss::launch_scan_lines_bounded_nocase : ss::launch_scan_lines_bounded; }

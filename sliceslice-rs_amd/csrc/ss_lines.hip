@@ -11,6 +11,8 @@
 //           lines read their bytes again and write the records at their rank.  A line longer than a tile, a workgroup's run or
 //           several of them is carried by the summaries alone.
 // The empty needle matches every line: the plain kernel in its EVERY form over the whole view, same combine.
+// The inverse of a call - the lines WITHOUT a match, ss_inverted.hip - is the same sum pass and, in place of the emit launches and
+// behind the combine, the three launches its LinesInverted names (lines_host.hpp); this file holds none of those kernels.
 // The launch shape is ss_matches.hip's (plan_static: the static one of an untuned search); the census is neither started nor read.
 #include "ss_internal.hpp"
 
@@ -87,23 +89,32 @@ struct LinesOut {
 
 // The parts' summaries -> the total (and the record of an unterminated last line), and - for the emit launches - the state in front
 // of every part: chunk summaries (many workgroups), ONE workgroup over the chunks, and the states spread back over the chunks.
-int combine_parts(const LinesScratch &sc, size_t len, const LinesOut &o, bool emit, hipStream_t st)
+// inv: the model's combine leaves its states and writes no record (capacity 0) and no second total; the total, the second one and the
+// last line's record are the inverted ones of inv->total behind it.
+int combine_parts(const LinesScratch &sc, size_t len, const LinesOut &o, bool emit, hipStream_t st, const LinesInverted *inv)
 {
     HIP_TRY(ss::launch_lines_chunks(sc.sum, sc.parts, sc.csum, sc.cpre, sc.pre, false, st));
-    const ss::CombineArgs ca = {sc.csum, sc.chunks, sc.cpre, sc.total, o.d_total2, len, o.begin, o.end, o.number, emit ? o.capacity : 0};
+    ss::CombineArgs ca = {sc.csum, sc.chunks, sc.cpre, sc.total, inv ? nullptr : o.d_total2, len, o.begin, o.end, o.number,
+                          emit && !inv ? o.capacity : 0};
     HIP_TRY(ss::launch_lines_combine(ca, st));
+    if (inv) {
+        ca.total2 = o.d_total2;
+        ca.capacity = emit ? o.capacity : 0;
+        HIP_TRY(inv->total(ca, st));
+    }
     if (emit) HIP_TRY(ss::launch_lines_chunks(sc.sum, sc.parts, sc.csum, sc.cpre, sc.pre, true, st));
     return SS_OK;
 }
 
-// Enqueues everything; *d_total = the scratch word that takes the total.  Preconditions: len >= 1, the needle holds no delimiter,
-// n <= len.
+// Enqueues everything; *d_total = the scratch word that takes the total.  Preconditions: len >= 1, and either every line is
+// selected (`every`: the empty needle - or, for an inverted call, a needle that no line can hold) or the needle holds no delimiter and
+// n <= len.  inv: the inverse of the call (lines_host.hpp), never together with `every`.
 int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, const void *d_hay, size_t len, int delimiter, hipStream_t st, const LinesOut &o,
-                  ScratchLease *lease, uint64_t **d_total, uint32_t bound)
+                  ScratchLease *lease, uint64_t **d_total, uint32_t bound, bool every, const LinesInverted *inv)
 {
     const uint8_t *hay = static_cast<const uint8_t *>(d_hay);
     const bool emit = o.capacity != 0 && (o.begin || o.end || o.number);
-    if (s->n == 0) {
+    if (every) {
         const uint64_t parts = (len + kPlainPart - 1) / kPlainPart;
         if (parts > 0x7fffffffull) return fail(SS_ERR_ARGUMENT, "haystack of %zu bytes is too long for the empty needle's pass", len);
         LinesScratch sc;
@@ -113,7 +124,7 @@ int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, con
         ss::LinePre *pre = sc.pre;
         ss::PlainArgs pa = {hay, 0, len, kPlainPart, sum, pre, o.begin, o.end, o.number, o.capacity, 0, (uint32_t)delimiter, ss::kLinesSum};
         HIP_TRY(ss::launch_lines_plain(pa, true, st));
-        if (int rc = combine_parts(sc, len, o, emit, st)) return rc;
+        if (int rc = combine_parts(sc, len, o, emit, st, nullptr)) return rc;
         if (emit) {
             pa.mode = ss::kLinesEmit;
             HIP_TRY(ss::launch_lines_plain(pa, true, st));
@@ -141,8 +152,15 @@ int enqueue_lines(ss::ScanLinesFn scan, const ss_searcher *s, PerDevice *pd, con
     if (!scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la, bound))
         return fail(SS_ERR_ARGUMENT, "no lines kernel for mode %d, window %d", ll.mode, ll.q);
     HIP_TRY(hipGetLastError());
-    if (int rc = combine_parts(sc, len, o, emit, st)) return rc;
-    if (emit) {
+    if (int rc = combine_parts(sc, len, o, emit, st, inv)) return rc;
+    if (emit && inv) {
+        // every part that closes a line without a match writes: the head too (it holds no match, so all of its lines are selected)
+        la.mode = head.mode = tail.mode = ss::kLinesEmit;
+        if (ll.head_end > 0) HIP_TRY(inv->plain(head, st));
+        (void)inv->emit(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la, bound);
+        HIP_TRY(hipGetLastError());
+        if (ll.tail_begin < len) HIP_TRY(inv->plain(tail, st));
+    } else if (emit) {
         la.mode = ss::kLinesEmit;
         (void)scan(ll.pr, ll.q, ll.mode, ll.one_byte, ll.shape, st, la, bound);
         HIP_TRY(hipGetLastError());
@@ -168,17 +186,30 @@ bool no_line(const ss_searcher *s, size_t len, int delimiter)
     return std::find(s->needle.begin(), s->needle.begin() + (long)s->n, (uint8_t)delimiter) != s->needle.begin() + (long)s->n;
 }
 
+// The answer that needs no launch, if there is one: no line matches - 0, or for an inverted call every line, which is the empty
+// needle's pass (*every) unless the view is empty; the empty needle matches every line, so its inverse selects none.
+bool settled(const ss_searcher *s, size_t len, int delimiter, const LinesInverted *inv, bool *every)
+{
+    *every = s->n == 0;
+    if (!inv) return no_line(s, len, delimiter);
+    if (len == 0 || s->n == 0) return true;
+    *every = no_line(s, len, delimiter);
+    return false;
+}
+
 int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter, void *hip_stream, const LinesOut &o,
-                   uint64_t *lines, uint32_t bound)
+                   uint64_t *lines, uint32_t bound, const LinesInverted *inv)
 {
     SearchGate gate(s);                                  // set_filter* are refused while this call runs
-    if (no_line(s, len, delimiter)) { *lines = 0; return SS_OK; }
+    bool every = false;
+    if (settled(s, len, delimiter, inv, &every)) { *lines = 0; return SS_OK; }
+    if (every) inv = nullptr;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     PerDevice *pd = nullptr;
     if (int rc = get_per_device(s, &pd)) return rc;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound, every, inv)) return rc;
     HIP_TRY(hipMemcpyAsync(lease.sc.h, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     lease.done = true;
@@ -190,14 +221,14 @@ int lines_blocking(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_hay
 
 // (lines_host.hpp: `scan` is launch_scan_lines, or its case-folding twin for ss_nocase.hip)
 int count_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
-                            void *hip_stream, uint64_t *lines, uint32_t bound)
+                            void *hip_stream, uint64_t *lines, uint32_t bound, const LinesInverted *inverted)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
-    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines, bound);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, LinesOut{}, lines, bound, inverted);
 }
 
 int count_lines_device_async_with(ss::ScanLinesFn scan, const char *name, const ss_searcher *s, const void *d_haystack, size_t len,
-                                  int delimiter, void *hip_stream, uint64_t *d_lines, uint32_t bound)
+                                  int delimiter, void *hip_stream, uint64_t *d_lines, uint32_t bound, const LinesInverted *inverted)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, d_lines)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -207,21 +238,23 @@ int count_lines_device_async_with(ss::ScanLinesFn scan, const char *name, const 
     PerDevice *pd = nullptr;
     if (int rc = get_per_device(s, &pd)) return rc;
     s->used_async.store(true, std::memory_order_release);
-    if (no_line(s, len, delimiter)) {
+    bool every = false;
+    if (settled(s, len, delimiter, inverted, &every)) {
         HIP_TRY(hipMemsetAsync(d_lines, 0, sizeof(uint64_t), st));
         return SS_OK;
     }
+    if (every) inverted = nullptr;
     LinesOut o;
     o.d_total2 = d_lines;
     ScratchLease lease;
     uint64_t *d_total = nullptr;
-    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound)) return rc;
+    if (int rc = enqueue_lines(scan, s, pd, d_haystack, len, delimiter, st, o, &lease, &d_total, bound, every, inverted)) return rc;
     return lease.release_on(st);
 }
 
 int find_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const void *d_haystack, size_t len, int delimiter,
                            void *hip_stream, uint64_t *d_begin, uint64_t *d_end, uint64_t *d_number, uint64_t capacity, uint64_t *lines,
-                           uint32_t bound)
+                           uint32_t bound, const LinesInverted *inverted)
 {
     if (int rc = check_args(s, d_haystack, len, delimiter, lines)) return rc;
     LinesOut o;
@@ -229,7 +262,7 @@ int find_lines_device_with(ss::ScanLinesFn scan, const ss_searcher *s, const voi
     o.end = d_end;
     o.number = d_number;
     o.capacity = capacity;
-    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, o, lines, bound);
+    return lines_blocking(scan, s, d_haystack, len, delimiter, hip_stream, o, lines, bound, inverted);
 }
 
 }  // namespace ssh

@@ -139,6 +139,13 @@ BOUNDED_ABI = {
     "ss_find_lines_bounded_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp, _vp, _vp, _u64, _pu64]),
 }
 SS_BOUND_WORD, SS_BOUND_LINE, SS_BOUND_NOCASE = 1, 2, 4
+# include/sliceslice_hip_inverted.h: the lines that do NOT match - libsliceslice_hip_inverted.so only (the bounded library's objects
+# plus the inverted kernels); the line calls' argument lists with `unsigned how` behind the delimiter, as in the bounded line calls
+INVERTED_ABI = {
+    "ss_count_lines_inverted_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _pu64]),
+    "ss_count_lines_inverted_device_async": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp]),
+    "ss_find_lines_inverted_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -230,8 +237,8 @@ def _bind(L, table, strict):
 
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
-# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES and _build.MORE_LIBRARIES under their names,
-# and the test hooks.
+# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
+# _build.YET_MORE_LIBRARIES under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -255,6 +262,9 @@ _FEATURES = {
     "bounded": (BOUNDED_ABI, "ss_count_bounded_device",
                 "whole_word=True / whole_line=True are not part of this library: they live in "
                 "libsliceslice_hip_bounded.so - create the searcher inside `with ss.bounded_build():`"),
+    "inverted": (INVERTED_ABI, "ss_count_lines_inverted_device",
+                 "the inverted line calls (count_lines_inverted / find_lines_inverted, grep -v) are not part of this library: they "
+                 "live in libsliceslice_hip_inverted.so - create the searcher inside `with ss.inverted_build():`"),
 }
 
 
@@ -300,8 +310,8 @@ def tools_lib():
 
 
 class _library_build:
-    """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES or
-    _build.MORE_LIBRARIES, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
+    _build.MORE_LIBRARIES or _build.YET_MORE_LIBRARIES, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -362,6 +372,14 @@ class bounded_build(_library_build):
     name = "bounded"
 
 
+class inverted_build(_library_build):
+    """libsliceslice_hip_inverted.so: the bounded library plus the lines that do NOT match (include/sliceslice_hip_inverted.h:
+    ``count_lines_inverted`` / ``count_lines_inverted_async`` / ``find_lines_inverted`` / ``find_lines_inverted_into`` of searchers
+    created inside the block - ``grep -v``; they take ``ignore_case``, ``whole_word`` and ``whole_line`` like their models).  There
+    is no inverted ``count`` / ``find_all``: occurrences have no complement."""
+    name = "inverted"
+
+
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
 
 
@@ -387,13 +405,16 @@ def _delimiter_byte(delimiter):
     return int(delimiter)
 
 
-def _scan_fn(L, name, ignore_case, whole_word=False, whole_line=False):
+def _scan_fn(L, name, ignore_case, whole_word=False, whole_line=False, invert=False):
     """The function `name` of the matches or the lines library from `L`, or - ignore_case - its folding form from the nocase
     library: ss_count_device -> ss_count_nocase_device, ss_find_lines_device -> ss_find_lines_nocase_device, ...
     whole_word / whole_line: its form in the bounded library (ss_count_bounded_device, ...) behind the SAME argument list - `how`
-    (SS_BOUND_WORD / SS_BOUND_LINE, | SS_BOUND_NOCASE with ignore_case) goes in front of the stream here."""
-    if whole_word or whole_line:
-        fn = getattr(_feature_lib(L, "bounded"), name.replace("_device", "_bounded_device"))
+    (SS_BOUND_WORD / SS_BOUND_LINE, | SS_BOUND_NOCASE with ignore_case) goes in front of the stream here.
+    invert (line functions only): the form in the inverted library (ss_count_lines_inverted_device, ...), whose `how` may also be 0
+    or SS_BOUND_NOCASE alone."""
+    if invert or whole_word or whole_line:
+        fn = getattr(_feature_lib(L, "inverted"), name.replace("_device", "_inverted_device")) if invert else \
+            getattr(_feature_lib(L, "bounded"), name.replace("_device", "_bounded_device"))
         how = (SS_BOUND_WORD if whole_word else 0) | (SS_BOUND_LINE if whole_line else 0) | (SS_BOUND_NOCASE if ignore_case else 0)
         at = 4 if "_lines_" in name else 3                  # (searcher, haystack, len[, delimiter], HOW, stream, ...)
         return lambda *a: fn(*a[:at], how, *a[at:])
@@ -460,6 +481,56 @@ class _on_device_of:
         if self._ctx is not None:
             self._ctx.__exit__(*a)
         return False
+
+
+# The four line methods of DynamicHipSearcher and their inverted twins (`invert`: the lines that do NOT match).  Functions of
+# the module, so that a call fails on the library's refusal before it touches anything else of the searcher.
+def _count_lines(s, invert, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+    fn = _scan_fn(s._L, "ss_count_lines_device", ignore_case, whole_word, whole_line, invert)
+    ptr, length, t = s._device_haystack(haystack)
+    c = _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        s._ck(fn(s._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
+    return c.value
+
+
+def _count_lines_async(s, invert, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+    fn = _scan_fn(s._L, "ss_count_lines_device_async", ignore_case, whole_word, whole_line, invert)
+    with _on_device_of(haystack):
+        st = stream if stream is not None else _current_stream_handle()
+        s._ck(fn(s._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
+
+
+def _find_lines(s, invert, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
+    import torch
+    count_fn, find_fn = _scan_fn(s._L, "ss_count_lines_device", ignore_case, whole_word, whole_line, invert), _scan_fn(s._L, "ss_find_lines_device", ignore_case, whole_word, whole_line, invert)
+    ptr, length, t = s._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    d = _delimiter_byte(delimiter)
+    total = _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        if capacity is None:
+            s._ck(count_fn(s._h, ptr, length, d, st, ctypes.byref(total)))
+            capacity = total.value
+        out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        p = [out[k].data_ptr() if capacity else None for k in range(3)]
+        s._ck(find_fn(s._h, ptr, length, d, st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
+    k = min(int(capacity), total.value)
+    return out[0, :k], out[1, :k], out[2, :k]
+
+
+def _find_lines_into(s, invert, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+    fn = _scan_fn(s._L, "ss_find_lines_device", ignore_case, whole_word, whole_line, invert)
+    ptr, length, t = s._device_haystack(haystack)
+    total = _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+        s._ck(fn(s._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
+    return total.value
+
 
 
 class DynamicHipSearcher:
@@ -630,20 +701,11 @@ class DynamicHipSearcher:
         """int: the number of lines of ``haystack`` (cut at every ``delimiter`` byte) that hold at least one occurrence of the
         needle - what ``grep -c`` prints (ss_count_lines_device).  Empty needle: the number of lines.  ignore_case=True folds the
         haystack's letters, never the delimiter."""
-        fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case, whole_word, whole_line)
-        ptr, length, t = self._device_haystack(haystack)
-        c = _u64(0)
-        with _on_device_of(t):
-            st = stream if stream is not None else _current_stream_handle()
-            self._ck(fn(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)))
-        return c.value
+        return _count_lines(self, False, haystack, delimiter, stream, ignore_case, whole_word, whole_line)
 
     def count_lines_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """Enqueue only (ss_count_lines_device_async): the count lands in the 8-byte device tensor ``d_count`` (overwritten)."""
-        fn = _scan_fn(self._L, "ss_count_lines_device_async", ignore_case, whole_word, whole_line)
-        with _on_device_of(haystack):
-            st = stream if stream is not None else _current_stream_handle()
-            self._ck(fn(self._h, haystack.data_ptr(), haystack.numel(), _delimiter_byte(delimiter), st, d_count.data_ptr()))
+        return _count_lines_async(self, False, haystack, d_count, delimiter, stream, ignore_case, whole_word, whole_line)
 
     def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """(begin, end, number): three int64 tensors on the haystack's device, one entry per matching line in ascending order - the
@@ -651,33 +713,32 @@ class DynamicHipSearcher:
         line number (ss_find_lines_device).  capacity=None: counted first (ss_count_lines_device: one more pass over the haystack, as
         ``find_all`` does), then exactly that many; with a capacity the haystack is read at most twice and the leftmost ``capacity``
         records come back."""
-        import torch
-        count_fn, find_fn = _scan_fn(self._L, "ss_count_lines_device", ignore_case, whole_word, whole_line), _scan_fn(self._L, "ss_find_lines_device", ignore_case, whole_word, whole_line)
-        ptr, length, t = self._device_haystack(haystack)
-        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
-        d = _delimiter_byte(delimiter)
-        total = _u64(0)
-        with _on_device_of(t):
-            st = stream if stream is not None else _current_stream_handle()
-            if capacity is None:
-                self._ck(count_fn(self._h, ptr, length, d, st, ctypes.byref(total)))
-                capacity = total.value
-            out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
-            p = [out[k].data_ptr() if capacity else None for k in range(3)]
-            self._ck(find_fn(self._h, ptr, length, d, st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
-        k = min(int(capacity), total.value)
-        return out[0, :k], out[1, :k], out[2, :k]
+        return _find_lines(self, False, haystack, delimiter, capacity, stream, ignore_case, whole_word, whole_line)
 
     def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         """ss_find_lines_device into the caller's 8-byte device tensors (each may be None: not wanted); returns the total count."""
-        fn = _scan_fn(self._L, "ss_find_lines_device", ignore_case, whole_word, whole_line)
-        ptr, length, t = self._device_haystack(haystack)
-        total = _u64(0)
-        with _on_device_of(t):
-            st = stream if stream is not None else _current_stream_handle()
-            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
-            self._ck(fn(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
-        return total.value
+        return _find_lines_into(self, False, haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    # -- the lines that do NOT hold it (libsliceslice_hip_inverted.so: searchers made inside `with ss.inverted_build():`) ----
+    # Methods of their own and not a keyword `invert` of the four above: tests/test_bounded_cpu.py pins the last parameters of those.
+    def count_lines_inverted(self, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        """int: the number of lines that ``count_lines`` with the same arguments does NOT count - ``grep -v -c``
+        (ss_count_lines_inverted_device).  Together the two are the number of lines.  Empty needle: 0; a needle longer than the
+        haystack or one that holds the delimiter: every line."""
+        return _count_lines(self, True, haystack, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def count_lines_inverted_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        """Enqueue only (ss_count_lines_inverted_device_async): the count lands in the 8-byte device tensor ``d_count``."""
+        return _count_lines_async(self, True, haystack, d_count, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def find_lines_inverted(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        """(begin, end, number) of the lines that ``find_lines`` with the same arguments does NOT return - ``grep -v -n``
+        (ss_find_lines_inverted_device).  capacity=None: sized from the inverted count."""
+        return _find_lines(self, True, haystack, delimiter, capacity, stream, ignore_case, whole_word, whole_line)
+
+    def find_lines_inverted_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        """ss_find_lines_inverted_device into the caller's 8-byte device tensors (each may be None); returns the total count."""
+        return _find_lines_into(self, True, haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
 
     # -- tuning / measurement hooks ------------------------------------------------------------------
     @property
@@ -815,6 +876,18 @@ class MemchrHipSearcher:
 
     def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         return self._inner.find_lines_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def count_lines_inverted(self, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.count_lines_inverted(haystack, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def count_lines_inverted_async(self, haystack, d_count, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.count_lines_inverted_async(haystack, d_count, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def find_lines_inverted(self, haystack, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.find_lines_inverted(haystack, delimiter, capacity, stream, ignore_case, whole_word, whole_line)
+
+    def find_lines_inverted_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
+        return self._inner.find_lines_inverted_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
 
 
 def shard_range(length, needle_len, nranks, rank):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""./grep_hip.py [-i] [-w | -x] <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
+"""./grep_hip.py [-i] [-w | -x] [-v] <needle> <file> [--count | --offsets | --count-lines | --lines] - the reference's examples/grep.rs:42-56 with the
 "hip" backend: map the file, build one searcher, one search_in, print the boolean.
   --count        the number of (overlapping) OCCURRENCES, not lines (libsliceslice_hip_matches.so, ss_count_device)
   --offsets      grep -b -o style: one byte offset per occurrence, ascending (ss_find_all_device)
@@ -13,6 +13,9 @@
                  ss_*_bounded_device calls).  Combines with -i.  The empty needle is refused.
   -x, --line-regexp  with --count-lines or --lines: only lines that ARE the needle (grep -x).  Combines with -i, not with -w; with
                  the occurrence outputs it is an error.
+  -v, --invert-match  with --count-lines or --lines: the lines that do NOT match (grep -v; libsliceslice_hip_inverted.so, the
+                 ss_*_lines_inverted_device calls).  Combines with -i, -w and -x.  There is no inverted occurrence form -
+                 occurrences have no complement - so --count and --offsets refuse it, and so do several patterns (-e / -f).
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
 per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched).  The batched
 library has no case-folding and no whole-word form: -i, -w and -x with -e / -f are refused."""
@@ -38,11 +41,12 @@ def count_patterns(patterns, filename):
         return counts.cpu().tolist()
 
 
-def matching_lines(searcher, data, ignore_case=False, **bound):
-    """[(number, line bytes)] of the lines that contain the needle: the records, then only those byte ranges, come to the host."""
+def matching_lines(searcher, data, ignore_case=False, invert=False, **bound):
+    """[(number, line bytes)] of the lines that contain the needle (invert: of those that do not): the records, then only those byte
+    ranges, come to the host."""
     import torch
     hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
-    begin, end, number = searcher.find_lines(hay, ignore_case=ignore_case, **bound)
+    begin, end, number = (searcher.find_lines_inverted if invert else searcher.find_lines)(hay, ignore_case=ignore_case, **bound)
     if begin.numel() == 0:
         return []
     # gather the matching lines' bytes on the device: one copy of sum(end - begin) bytes instead of the whole file
@@ -70,10 +74,14 @@ def main():
     fold = "-i" in argv or "--ignore-case" in argv
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
-    argv = [a for a in argv if a not in ("-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp")]
+    invert = "-v" in argv or "--invert-match" in argv
+    argv = [a for a in argv if a not in ("-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp", "-v", "--invert-match")]
     args = [a for a in argv if not a.startswith("--")]
     flags = {a for a in argv if a.startswith("--")}
     if patterns:
+        if invert:
+            raise SystemExit("./grep_hip.py: -v is not available with -e / -f: several patterns go through the batched library, which "
+                             "counts occurrences, and occurrences have no complement - run one pattern per call with --count-lines")
         if word or line:
             raise SystemExit("./grep_hip.py: -w / -x are not available with -e / -f: several patterns go through the batched library, "
                              "which has no whole-word form - run one pattern per call")
@@ -85,9 +93,26 @@ def main():
         sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
         return
     if len(args) < 2 or flags - {"--count", "--offsets", "--count-lines", "--lines", "--rare-position"}:
-        raise SystemExit("./grep_hip.py [-i | --ignore-case] [-w | --word-regexp | -x | --line-regexp] <needle> <file> "
-                         "[--count | --offsets | --count-lines | --lines]")
+        raise SystemExit("./grep_hip.py [-i | --ignore-case] [-w | --word-regexp | -x | --line-regexp] [-v | --invert-match] <needle> "
+                         "<file> [--count | --offsets | --count-lines | --lines]")
     needle, filename = args[0].encode(), args[1]
+    if invert:
+        if flags & {"--count", "--offsets"} or not flags & {"--count-lines", "--lines"}:
+            raise SystemExit("./grep_hip.py: -v is about lines: it goes with --count-lines or --lines; --count and --offsets are about "
+                             "occurrences, which have no complement")
+        if word and line:
+            raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
+        if (word or line) and not needle:
+            raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
+        with ss.inverted_build():
+            searcher = ss.DynamicHipSearcher.new_nocase(needle) if fold else ss.DynamicHipSearcher.new(needle)
+        data = open(filename, "rb").read()
+        if "--lines" in flags:
+            for n, text in matching_lines(searcher, data, ignore_case=fold, invert=True, whole_word=word, whole_line=line):
+                sys.stdout.buffer.write(b"%d:%s\n" % (n, text))
+        else:
+            print(searcher.count_lines_inverted(data, ignore_case=fold, whole_word=word, whole_line=line))
+        return
     if word or line:
         if word and line:
             raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
