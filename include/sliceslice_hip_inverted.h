@@ -40,8 +40,9 @@
  * the haystack a second time wherever a part closes a selected line below the capacity, which for most needles is nearly
  * everywhere.  Rates measured on an MI355X are in DESIGN.md 5.11.
  *
- * Out of scope: batched, plan, sharded, service and host / file forms; context lines (-A / -B / -C); -m; the empty needle with
- * -w / -x; multi-byte terminators; regular expressions.
+ * Out of scope: batched, plan, sharded, service and host / file forms; context lines (-A / -B / -C: they are
+ * sliceslice_hip_context.h's, which takes these calls as models); -m; the empty needle with -w / -x; multi-byte terminators;
+ * regular expressions.
  */
 #ifndef SLICESLICE_HIP_INVERTED_H
 #define SLICESLICE_HIP_INVERTED_H

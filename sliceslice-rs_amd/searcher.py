@@ -146,6 +146,14 @@ INVERTED_ABI = {
     "ss_count_lines_inverted_device_async": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp]),
     "ss_find_lines_inverted_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _vp, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_context.h: matching lines with their context lines, and the records of any set of line numbers -
+# libsliceslice_hip_context.so only (the inverted library's objects plus the context kernels)
+CONTEXT_ABI = {
+    "ss_lines_around_device": (_int, [_vp, _vp, _sz, _int, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _pu64]),
+    "ss_find_lines_context_device": (_int, [_vp, _vp, _sz, _int, _uint, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _pu64, _pu64]),
+}
+SS_CONTEXT_INVERT = 8
+CONTEXT_PART_BYTES = 65536          # SS_CONTEXT_PART_BYTES: bytes of the view per workgroup of the delimiter census
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -238,7 +246,7 @@ def _bind(L, table, strict):
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
 # _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES under their names, and the test hooks.
+# _build.YET_MORE_LIBRARIES and _build.ONE_MORE_LIBRARY under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -265,6 +273,9 @@ _FEATURES = {
     "inverted": (INVERTED_ABI, "ss_count_lines_inverted_device",
                  "the inverted line calls (count_lines_inverted / find_lines_inverted, grep -v) are not part of this library: they "
                  "live in libsliceslice_hip_inverted.so - create the searcher inside `with ss.inverted_build():`"),
+    "context": (CONTEXT_ABI, "ss_lines_around_device",
+                "the context calls (find_lines_context / lines_around, grep -A / -B / -C) are not part of this library: they "
+                "live in libsliceslice_hip_context.so - create the searcher inside `with ss.context_build():`"),
 }
 
 
@@ -311,7 +322,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES or _build.YET_MORE_LIBRARIES, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES or _build.ONE_MORE_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -378,6 +389,14 @@ class inverted_build(_library_build):
     created inside the block - ``grep -v``; they take ``ignore_case``, ``whole_word`` and ``whole_line`` like their models).  There
     is no inverted ``count`` / ``find_all``: occurrences have no complement."""
     name = "inverted"
+
+
+class context_build(_library_build):
+    """libsliceslice_hip_context.so: the inverted library plus matching lines with their context lines
+    (include/sliceslice_hip_context.h: ``find_lines_context`` / ``find_lines_context_into`` - ``grep -A / -B / -C``; they take
+    ``ignore_case``, ``whole_word``, ``whole_line`` and ``invert`` - and ``lines_around`` / ``lines_around_into``, the records and the
+    context of any ascending set of line numbers, of searchers created inside the block)."""
+    name = "context"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -531,6 +550,110 @@ def _find_lines_into(s, invert, haystack, d_begin, d_end, d_number, capacity, de
         s._ck(fn(s._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity), ctypes.byref(total)))
     return total.value
 
+
+# The four context methods of DynamicHipSearcher (include/sliceslice_hip_context.h), functions of the module for the same reason.
+_U64_MAX = (1 << 64) - 1
+
+
+def _context_amount(value, what):
+    value = int(value)
+    if not 0 <= value <= _U64_MAX:
+        raise ValueError("%s is a number of lines, 0 .. 2^64 - 1, got %d" % (what, value))
+    return value
+
+
+def _context_how(ignore_case, whole_word, whole_line, invert):
+    return (SS_BOUND_WORD if whole_word else 0) | (SS_BOUND_LINE if whole_line else 0) | (SS_BOUND_NOCASE if ignore_case else 0) | \
+        (SS_CONTEXT_INVERT if invert else 0)
+
+
+def _device_numbers(numbers, dev):
+    """The line numbers of lines_around as an int64 device tensor (a tensor on the device is taken as it is)."""
+    import torch
+    if _is_tensor(numbers):
+        if numbers.dtype not in (torch.int64, torch.uint64):
+            raise TypeError("line numbers are 64-bit integers")
+        return numbers.contiguous().to(dev)
+    a = np.ascontiguousarray(np.asarray(numbers, dtype=np.uint64)).view(np.int64).reshape(-1)
+    return torch.from_numpy(a.copy()).to(dev)
+
+
+def _context_arrays(capacity, dev):
+    import torch
+    n = max(int(capacity), 1)
+    return torch.empty((3, n), dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+
+
+def _find_lines_context_into(s, haystack, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None,
+                             ignore_case=False, whole_word=False, whole_line=False, invert=False):
+    fn = _feature_lib(s._L, "context").ss_find_lines_context_device
+    ptr, length, t = s._device_haystack(haystack)
+    total, selected = _u64(0), _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number, d_kind)]
+        s._ck(fn(s._h, ptr, length, _delimiter_byte(delimiter), _context_how(ignore_case, whole_word, whole_line, invert),
+                 _context_amount(before, "before"), _context_amount(after, "after"), st, p[0], p[1], p[2], p[3], int(capacity),
+                 ctypes.byref(total), ctypes.byref(selected)))
+    return total.value, selected.value
+
+
+def _find_lines_context(s, haystack, before=0, after=0, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False,
+                        whole_line=False, invert=False):
+    import torch
+    _feature_lib(s._L, "context")
+    ptr, length, t = s._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    kw = dict(before=before, after=after, delimiter=delimiter, stream=stream, ignore_case=ignore_case, whole_word=whole_word,
+              whole_line=whole_line, invert=invert)
+    hay = t if t is not None else (ptr, length)
+    if capacity is None:
+        capacity, _ = _find_lines_context_into(s, hay, None, None, None, None, 0, **kw)
+    out, kind = _context_arrays(capacity, dev)
+    p = [out[k] if capacity else None for k in range(3)] + [kind if capacity else None]
+    total, _ = _find_lines_context_into(s, hay, p[0], p[1], p[2], p[3], capacity, **kw)
+    k = min(int(capacity), total)
+    return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+
+def _lines_around_into(s, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None):
+    import torch
+    fn = _feature_lib(s._L, "context").ss_lines_around_device
+    ptr, length, t = s._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    total = _u64(0)
+    with _on_device_of(t):
+        d_numbers = _device_numbers(numbers, dev)
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number, d_kind)]
+        s._ck(fn(s._h, ptr, length, _delimiter_byte(delimiter), d_numbers.data_ptr() if d_numbers.numel() else None, d_numbers.numel(),
+                 _context_amount(before, "before"), _context_amount(after, "after"), st, p[0], p[1], p[2], p[3], int(capacity),
+                 ctypes.byref(total)))
+    return total.value
+
+
+def _lines_around(s, haystack, numbers, before=0, after=0, delimiter=b"\n", capacity=None, stream=None):
+    import torch
+    _feature_lib(s._L, "context")
+    ptr, length, t = s._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    hay = t if t is not None else (ptr, length)
+    with _on_device_of(t):
+        numbers = _device_numbers(numbers, dev)
+    kw = dict(before=before, after=after, delimiter=delimiter, stream=stream)
+    if capacity is None:
+        capacity = _lines_around_into(s, hay, numbers, None, None, None, None, 0, **kw)
+    out, kind = _context_arrays(capacity, dev)
+    p = [out[k] if capacity else None for k in range(3)] + [kind if capacity else None]
+    total = _lines_around_into(s, hay, numbers, p[0], p[1], p[2], p[3], capacity, **kw)
+    k = min(int(capacity), total)
+    return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+
+def lines_around(haystack, numbers, before=0, after=0, delimiter=b"\n", capacity=None, stream=None):
+    """``DynamicHipSearcher.lines_around`` through a throw-away searcher (the call needs one for the device and its scratch only;
+    inside ``with ss.context_build():``)."""
+    return DynamicHipSearcher.new(b"").lines_around(haystack, numbers, before, after, delimiter, capacity, stream)
 
 
 class DynamicHipSearcher:
@@ -740,6 +863,31 @@ class DynamicHipSearcher:
         """ss_find_lines_inverted_device into the caller's 8-byte device tensors (each may be None); returns the total count."""
         return _find_lines_into(self, True, haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
 
+    # -- with their context lines (libsliceslice_hip_context.so: searchers made inside `with ss.context_build():`) ------------
+    def find_lines_context(self, haystack, before=0, after=0, delimiter=b"\n", capacity=None, stream=None,
+                           ignore_case=False, whole_word=False, whole_line=False, invert=False):
+        """(begin, end, number, kind): the records of the selected lines AND of the ``before`` lines in front of and the ``after``
+        lines behind each of them, every line once, ascending - ``grep -B before -A after -n`` (ss_find_lines_context_device).
+        kind (uint8) is 1 for a selected line and 0 for a context line; ``--`` stands wherever two consecutive numbers differ by
+        more than one.  invert=True: the model is ``find_lines_inverted``.  capacity=None: counted first, then sized exactly."""
+        return _find_lines_context(self, haystack, before, after, delimiter, capacity, stream, ignore_case, whole_word, whole_line, invert)
+
+    def find_lines_context_into(self, haystack, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None,
+                                ignore_case=False, whole_word=False, whole_line=False, invert=False):
+        """ss_find_lines_context_device into the caller's device tensors (8-byte x3, 1-byte kind; each may be None); returns
+        (total, selected): the size of the output and the number of selected lines."""
+        return _find_lines_context_into(self, haystack, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream,
+                                        ignore_case, whole_word, whole_line, invert)
+
+    def lines_around(self, haystack, numbers, before=0, after=0, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number, kind) for the 1-based, strictly ascending line ``numbers`` (a sequence or a 64-bit tensor) and their
+        context lines (ss_lines_around_device; the needle is not looked at).  before = after = 0: the records of the listed lines."""
+        return _lines_around(self, haystack, numbers, before, after, delimiter, capacity, stream)
+
+    def lines_around_into(self, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None):
+        """ss_lines_around_device into the caller's device tensors (each may be None); returns the size of the output."""
+        return _lines_around_into(self, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream)
+
     # -- tuning / measurement hooks ------------------------------------------------------------------
     @property
     def filter(self):
@@ -888,6 +1036,21 @@ class MemchrHipSearcher:
 
     def find_lines_inverted_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):
         return self._inner.find_lines_inverted_into(haystack, d_begin, d_end, d_number, capacity, delimiter, stream, ignore_case, whole_word, whole_line)
+
+    def find_lines_context(self, haystack, before=0, after=0, delimiter=b"\n", capacity=None, stream=None,
+                           ignore_case=False, whole_word=False, whole_line=False, invert=False):
+        return self._inner.find_lines_context(haystack, before, after, delimiter, capacity, stream, ignore_case, whole_word, whole_line, invert)
+
+    def find_lines_context_into(self, haystack, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None,
+                                ignore_case=False, whole_word=False, whole_line=False, invert=False):
+        return self._inner.find_lines_context_into(haystack, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream,
+                                                   ignore_case, whole_word, whole_line, invert)
+
+    def lines_around(self, haystack, numbers, before=0, after=0, delimiter=b"\n", capacity=None, stream=None):
+        return self._inner.lines_around(haystack, numbers, before, after, delimiter, capacity, stream)
+
+    def lines_around_into(self, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None):
+        return self._inner.lines_around_into(haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream)
 
 
 def shard_range(length, needle_len, nranks, rank):

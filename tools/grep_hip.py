@@ -16,6 +16,11 @@
   -v, --invert-match  with --count-lines or --lines: the lines that do NOT match (grep -v; libsliceslice_hip_inverted.so, the
                  ss_*_lines_inverted_device calls).  Combines with -i, -w and -x.  There is no inverted occurrence form -
                  occurrences have no complement - so --count and --offsets refuse it, and so do several patterns (-e / -f).
+  -A NUM, -B NUM, -C NUM (--after-context, --before-context, --context; also -ANUM and --context=NUM)  with --lines only: NUM
+                 lines behind / in front of / around every selected line as well, each line once - `number:line` for the selected
+                 lines, `number-line` for the context lines and `--` between groups that are not adjacent, byte for byte what
+                 `LC_ALL=C grep -F -n` prints (libsliceslice_hip_context.so, ss_find_lines_context_device).  Combines with -i, -w,
+                 -x and -v.  The counting outputs, the plain search and several patterns (-e / -f) refuse them.
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
 per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched).  The batched
 library has no case-folding and no whole-word form: -i, -w and -x with -e / -f are refused."""
@@ -61,14 +66,58 @@ def matching_lines(searcher, data, ignore_case=False, invert=False, **bound):
     return out
 
 
+_CONTEXT_FLAGS = {"-A": "after", "--after-context": "after", "-B": "before", "--before-context": "before", "-C": "both", "--context": "both"}
+
+
+def context_amount(flag, text):
+    if not (text.isascii() and text.isdigit()):
+        raise SystemExit("./grep_hip.py: %s takes a non-negative integer (a number of context lines), got %r" % (flag, text))
+    return int(text)
+
+
+def context_lines(searcher, data, before, after, ignore_case=False, invert=False, **bound):
+    """grep's output for -B before -A after -n, as bytes: like matching_lines, the records first, then only the bytes of the
+    printed lines, gathered on the device."""
+    import torch
+    hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+    begin, end, number, kind = searcher.find_lines_context(hay, min(before, 2 ** 64 - 1), min(after, 2 ** 64 - 1), ignore_case=ignore_case,
+                                                           invert=invert, **bound)
+    if begin.numel() == 0:
+        return b""
+    length = end - begin
+    start = torch.cumsum(length, 0) - length
+    idx = torch.repeat_interleave(begin - start, length) + torch.arange(int(length.sum()), device=hay.device)
+    packed = hay[idx].cpu().numpy().tobytes()
+    out, at, last = [], 0, None
+    for n, ln, k in zip(number.cpu().tolist(), length.cpu().tolist(), kind.cpu().tolist()):
+        if last is not None and n > last + 1:
+            out.append(b"--\n")
+        out.append(b"%d%s%s\n" % (n, b":" if k else b"-", packed[at:at + ln]))
+        at += ln
+        last = n
+    return b"".join(out)
+
+
 def main():
-    argv, patterns = [], []
+    argv, patterns, context = [], [], {}
     it = iter(sys.argv[1:])
     for a in it:
         if a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
             patterns += [l for l in open(next(it), "rb").read().split(b"\n") if l]
+        elif a in _CONTEXT_FLAGS or a[:2] in ("-A", "-B", "-C") or a.split("=", 1)[0] in _CONTEXT_FLAGS:
+            if a in _CONTEXT_FLAGS:
+                flag, text = a, next(it, "")
+            elif a.startswith("--"):
+                flag, text = a.split("=", 1)
+            else:
+                flag, text = a[:2], a[2:]
+            amount = context_amount(flag, text)
+            for side in ("before", "after"):
+                if _CONTEXT_FLAGS[flag] in (side, "both"):
+                    context[side] = amount
+            context["flag"] = flag
         else:
             argv.append(a)
     fold = "-i" in argv or "--ignore-case" in argv
@@ -88,14 +137,32 @@ def main():
         if fold:
             raise SystemExit("./grep_hip.py: -i is not available with -e / -f: several patterns go through the batched library, "
                              "which has no case-folding form - run one pattern per call")
+        if context:
+            raise SystemExit("./grep_hip.py: %s is not available with -e / -f: several patterns go through the batched library, which "
+                             "counts occurrences and knows no lines - run one pattern per call with --lines" % context["flag"])
         if len(args) != 1 or flags != {"--count"}:
             raise SystemExit("./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file>")
         sys.stdout.write("".join("%d\n" % c for c in count_patterns(patterns, args[0])))
         return
     if len(args) < 2 or flags - {"--count", "--offsets", "--count-lines", "--lines", "--rare-position"}:
-        raise SystemExit("./grep_hip.py [-i | --ignore-case] [-w | --word-regexp | -x | --line-regexp] [-v | --invert-match] <needle> "
+        raise SystemExit("./grep_hip.py [-i | --ignore-case] [-w | --word-regexp | -x | --line-regexp] [-v | --invert-match] "
+                         "[-A NUM | --after-context=NUM] [-B NUM | --before-context=NUM] [-C NUM | --context=NUM] <needle> "
                          "<file> [--count | --offsets | --count-lines | --lines]")
     needle, filename = args[0].encode(), args[1]
+    if context:
+        if flags & {"--count", "--offsets", "--count-lines"} or "--lines" not in flags:
+            raise SystemExit("./grep_hip.py: %s adds context LINES to the lines that --lines prints: it goes with --lines only; --count, "
+                             "--offsets and --count-lines print numbers, and the plain search prints one word" % context["flag"])
+        if word and line:
+            raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
+        if (word or line) and not needle:
+            raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
+        with ss.context_build():
+            searcher = ss.DynamicHipSearcher.new_nocase(needle) if fold else ss.DynamicHipSearcher.new(needle)
+        data = open(filename, "rb").read()
+        sys.stdout.buffer.write(context_lines(searcher, data, context.get("before", 0), context.get("after", 0), ignore_case=fold,
+                                              invert=invert, whole_word=word, whole_line=line))
+        return
     if invert:
         if flags & {"--count", "--offsets"} or not flags & {"--count-lines", "--lines"}:
             raise SystemExit("./grep_hip.py: -v is about lines: it goes with --count-lines or --lines; --count and --offsets are about "

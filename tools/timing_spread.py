@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The noise model of the timing tests: runs `pytest -m "gpu and timing"` N times (default 10) with SS_TIMING_LOG set, and
 summarises what the tests measured - min / median / max per quantity, and whether every run was green.
-    python tools/timing_spread.py [runs=10] > profiles/r05/timing_test_spread.jsonl"""
+    python tools/timing_spread.py [runs=10] > profiles/r05/timing_test_spread.jsonl
+    python tools/timing_spread.py 10 tests/test_gpu_zz_context_timing.py > ...      (one file's tests only; default: all of tests/)"""
 import json
 import os
 import subprocess
@@ -14,11 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     runs = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    targets = [os.path.join(ROOT, a) for a in sys.argv[2:]] or [os.path.join(ROOT, "tests")]
     log = tempfile.mktemp(prefix="ss_timing_", suffix=".jsonl", dir="/tmp")
     outcomes = []
     for k in range(runs):
         t0 = time.time()
-        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests"), "-q", "-m", "gpu and timing", "-p", "no:cacheprovider"],
+        r = subprocess.run([sys.executable, "-m", "pytest"] + targets + ["-q", "-m", "gpu and timing", "-p", "no:cacheprovider"],
                            cwd=ROOT, env=dict(os.environ, SS_TIMING_LOG=log), capture_output=True, text=True)
         tail = [l for l in r.stdout.splitlines() if " passed" in l or " failed" in l]
         outcomes.append({"run": k, "rc": r.returncode, "seconds": round(time.time() - t0, 1), "summary": tail[-1] if tail else r.stdout[-200:]})
