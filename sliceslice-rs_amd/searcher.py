@@ -154,6 +154,16 @@ CONTEXT_ABI = {
 }
 SS_CONTEXT_INVERT = 8
 CONTEXT_PART_BYTES = 65536          # SS_CONTEXT_PART_BYTES: bytes of the view per workgroup of the delimiter census
+# include/sliceslice_hip_anyof.h: the lines that match any of several needles, and the ordered union of ascending lists of line
+# numbers - libsliceslice_hip_anyof.so only (the context library's objects plus the union kernels)
+_u32 = ctypes.c_uint32
+ANYOF_ABI = {
+    "ss_union_numbers_device": (_int, [_vp, _vp, _vp, _u32, _u64, _int, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_anyof_device": (_int, [_vp, _u32, _vp, _sz, _int, _uint, _vp, _pu64]),
+    "ss_find_lines_anyof_device": (_int, [_vp, _u32, _vp, _sz, _int, _uint, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _pu64, _pu64]),
+}
+ANYOF_MAX_NEEDLES = 65536           # SS_ANYOF_MAX_NEEDLES: needles (or lists) per call
+ANYOF_SEGMENT_LINES = 65536         # SS_ANYOF_SEGMENT_LINES: line numbers per workgroup of the union kernels
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -246,7 +256,7 @@ def _bind(L, table, strict):
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
 # _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES and _build.ONE_MORE_LIBRARY under their names, and the test hooks.
+# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY and _build.NEXT_LIBRARY under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -276,6 +286,9 @@ _FEATURES = {
     "context": (CONTEXT_ABI, "ss_lines_around_device",
                 "the context calls (find_lines_context / lines_around, grep -A / -B / -C) are not part of this library: they "
                 "live in libsliceslice_hip_context.so - create the searcher inside `with ss.context_build():`"),
+    "anyof": (ANYOF_ABI, "ss_union_numbers_device",
+              "the several-needle calls (count_lines_anyof / find_lines_anyof / union_numbers, grep -e A -e B) are not part of this "
+              "library: they live in libsliceslice_hip_anyof.so - create the searchers inside `with ss.anyof_build():`"),
 }
 
 
@@ -322,7 +335,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES or _build.ONE_MORE_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY or _build.NEXT_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -397,6 +410,15 @@ class context_build(_library_build):
     ``ignore_case``, ``whole_word``, ``whole_line`` and ``invert`` - and ``lines_around`` / ``lines_around_into``, the records and the
     context of any ascending set of line numbers, of searchers created inside the block)."""
     name = "context"
+
+
+class anyof_build(_library_build):
+    """libsliceslice_hip_anyof.so: the context library plus the lines that match ANY OF SEVERAL NEEDLES
+    (include/sliceslice_hip_anyof.h: ``ss.count_lines_anyof`` / ``ss.find_lines_anyof`` / ``ss.find_lines_anyof_into`` -
+    ``grep -e A -e B`` / ``grep -f FILE``; they take ``ignore_case``, ``whole_word``, ``whole_line`` and ``invert``, and the find
+    calls ``before`` / ``after`` - of searchers created inside the block, and ``ss.union_numbers`` / ``ss.union_numbers_into``, the
+    ordered union of ascending lists of line numbers or its complement)."""
+    name = "anyof"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -654,6 +676,118 @@ def lines_around(haystack, numbers, before=0, after=0, delimiter=b"\n", capacity
     """``DynamicHipSearcher.lines_around`` through a throw-away searcher (the call needs one for the device and its scratch only;
     inside ``with ss.context_build():``)."""
     return DynamicHipSearcher.new(b"").lines_around(haystack, numbers, before, after, delimiter, capacity, stream)
+
+
+# The several-needle calls (include/sliceslice_hip_anyof.h): functions of the module, since no searcher owns them.
+def _anyof_table(searchers):
+    """(the library, the table of handles, its length) of a non-empty sequence of searchers made inside ``with ss.anyof_build():``."""
+    inner = [getattr(s, "_inner", s) for s in searchers]
+    L = _feature_lib(inner[0]._L if inner else lib(), "anyof")
+    if not inner:
+        raise SlicesliceError(SS_ERR_ARGUMENT, "the several-needle calls take at least one searcher")
+    if any(s._L is not L for s in inner):
+        raise SlicesliceError(SS_ERR_ARGUMENT, "the searchers of a several-needle call belong to one library: create all of them inside "
+                                               "one `with ss.anyof_build():`")
+    return L, inner, (ctypes.c_void_p * len(inner))(*[s._h for s in inner])
+
+
+def count_lines_anyof(searchers, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False, invert=False):
+    """The number of lines that hold ANY of the searchers' needles - ``grep -c -e A -e B`` (ss_count_lines_anyof_device); with
+    ``invert`` the lines that hold none of them.  The flags apply to every needle."""
+    L, inner, table = _anyof_table(searchers)
+    ptr, length, t = inner[0]._device_haystack(haystack)
+    c = _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        _check(L.ss_count_lines_anyof_device(table, len(inner), ptr, length, _delimiter_byte(delimiter),
+                                             _context_how(ignore_case, whole_word, whole_line, invert), st, ctypes.byref(c)), L)
+    return c.value
+
+
+def find_lines_anyof_into(searchers, haystack, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None,
+                          ignore_case=False, whole_word=False, whole_line=False, invert=False):
+    """ss_find_lines_anyof_device into the caller's device tensors (8-byte x3, 1-byte kind; each may be None); returns
+    (total, selected)."""
+    L, inner, table = _anyof_table(searchers)
+    ptr, length, t = inner[0]._device_haystack(haystack)
+    total, selected = _u64(0), _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number, d_kind)]
+        _check(L.ss_find_lines_anyof_device(table, len(inner), ptr, length, _delimiter_byte(delimiter),
+                                            _context_how(ignore_case, whole_word, whole_line, invert), _context_amount(before, "before"),
+                                            _context_amount(after, "after"), st, p[0], p[1], p[2], p[3], int(capacity), ctypes.byref(total),
+                                            ctypes.byref(selected)), L)
+    return total.value, selected.value
+
+
+def find_lines_anyof(searchers, haystack, before=0, after=0, delimiter=b"\n", capacity=None, stream=None, ignore_case=False, whole_word=False,
+                     whole_line=False, invert=False):
+    """(begin, end, number, kind) of the lines that hold ANY of the searchers' needles, with ``before`` lines in front of and
+    ``after`` lines behind each of them, every line once, ascending - ``grep -n -e A -e B`` with ``-B`` / ``-A``
+    (ss_find_lines_anyof_device); kind is 1 for a selected line and 0 for a context line."""
+    import torch
+    L, inner, table = _anyof_table(searchers)
+    ptr, length, t = inner[0]._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    kw = dict(before=before, after=after, delimiter=delimiter, stream=stream, ignore_case=ignore_case, whole_word=whole_word,
+              whole_line=whole_line, invert=invert)
+    hay = t if t is not None else (ptr, length)
+    if capacity is None:
+        capacity, _ = find_lines_anyof_into(searchers, hay, None, None, None, None, 0, **kw)
+    out, kind = _context_arrays(capacity, dev)
+    p = [out[k] if capacity else None for k in range(3)] + [kind if capacity else None]
+    total, _ = find_lines_anyof_into(searchers, hay, p[0], p[1], p[2], p[3], capacity, **kw)
+    k = min(int(capacity), total)
+    return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+
+_UNION_SEARCHERS = {}            # library -> the searcher that union_numbers hands to ss_union_numbers_device
+
+
+def _union_lists(lists, dev):
+    """(the lists' numbers in one int64 device tensor, their CSR offsets as a ctypes array, their number)"""
+    import torch
+    parts = [_device_numbers(l, dev).reshape(-1) for l in lists]
+    offsets = [0]
+    for q in parts:
+        offsets.append(offsets[-1] + q.numel())
+    flat = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64, device=dev)
+    return flat, (ctypes.c_uint64 * len(offsets))(*offsets), len(parts)
+
+
+def union_numbers_into(lists, limit, d_out, capacity, complement=False, stream=None):
+    """ss_union_numbers_device into the caller's 8-byte device tensor (None: count only); returns the size of the union.  Inside
+    ``with ss.anyof_build():``."""
+    import torch
+    L = _feature_lib(lib(), "anyof")
+    dev = d_out.device if d_out is not None else next((l.device for l in lists if _is_tensor(l) and l.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    s = _UNION_SEARCHERS.get(id(L)) or _UNION_SEARCHERS.setdefault(id(L), DynamicHipSearcher.new(b""))     # (the call needs one for
+                                                                                                           # the device and its scratch only)
+    total = _u64(0)
+    with _on_device_of(d_out):
+        flat, offsets, n = _union_lists(lists, dev)
+        st = stream if stream is not None else _current_stream_handle()
+        _check(L.ss_union_numbers_device(s._h, flat.data_ptr() if flat.numel() else None, offsets, n, int(limit), 1 if complement else 0, st,
+                                         d_out.data_ptr() if d_out is not None else None, int(capacity), ctypes.byref(total)), L)
+    return total.value
+
+
+def union_numbers(lists, limit, complement=False, capacity=None, stream=None):
+    """The ascending union of the strictly ascending ``lists`` of line numbers (sequences, arrays or device tensors), each value
+    once - or with ``complement`` every number of 1 .. limit that is in no list - as an int64 device tensor of
+    min(total, capacity) numbers (ss_union_numbers_device).  A 0 and a number above ``limit`` select nothing.  Inside
+    ``with ss.anyof_build():``."""
+    import torch
+    _feature_lib(lib(), "anyof")
+    lists = list(lists)
+    dev = next((l.device for l in lists if _is_tensor(l) and l.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    lists = [_device_numbers(l, dev) for l in lists]
+    if capacity is None:
+        capacity = union_numbers_into(lists, limit, None, 0, complement, stream)
+    out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+    total = union_numbers_into(lists, limit, out if capacity else None, capacity, complement, stream)
+    return out[:min(int(capacity), total)]
 
 
 class DynamicHipSearcher:

@@ -23,7 +23,13 @@
                  -x and -v.  The counting outputs, the plain search and several patterns (-e / -f) refuse them.
 ./grep_hip.py --count (-e <pattern>)... [-f <patterns file>] <file> - several patterns (-e repeated; -f: one per line): one count
 per pattern and line, in the order given, from ONE call (libsliceslice_hip_matches_batched.so, ss_count_batched).  The batched
-library has no case-folding and no whole-word form: -i, -w and -x with -e / -f are refused."""
+library has no case-folding and no whole-word form: -i, -w and -x with -e / -f and --count are refused.
+./grep_hip.py (--count-lines | --lines) [-i] [-w | -x] [-v] [-A NUM] [-B NUM] [-C NUM] (-e <pattern>)... [-f <patterns file>] <file> -
+the LINES that match ANY of the patterns (grep -e A -e B, grep -f FILE; -e may also stand once): --count-lines prints their
+number, --lines prints `number:line` for each - and, with -A / -B / -C (--lines only), the context lines as `number-line` and `--`
+between groups - byte for byte what `LC_ALL=C grep -F -c` / `LC_ALL=C grep -F -n` print (libsliceslice_hip_anyof.so,
+ss_count_lines_anyof_device / ss_find_lines_anyof_device: one searcher per pattern, the flags apply to every pattern; -v selects
+the lines that match none)."""
 import os
 import sys
 
@@ -80,8 +86,11 @@ def context_lines(searcher, data, before, after, ignore_case=False, invert=False
     printed lines, gathered on the device."""
     import torch
     hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
-    begin, end, number, kind = searcher.find_lines_context(hay, min(before, 2 ** 64 - 1), min(after, 2 ** 64 - 1), ignore_case=ignore_case,
-                                                           invert=invert, **bound)
+    if isinstance(searcher, list):                              # several patterns: the lines that match any of them
+        find = lambda *a, **kw: ss.find_lines_anyof(searcher, *a, **kw)                  # noqa: E731
+    else:
+        find = searcher.find_lines_context
+    begin, end, number, kind = find(hay, min(before, 2 ** 64 - 1), min(after, 2 ** 64 - 1), ignore_case=ignore_case, invert=invert, **bound)
     if begin.numel() == 0:
         return b""
     length = end - begin
@@ -127,10 +136,33 @@ def main():
     argv = [a for a in argv if a not in ("-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp", "-v", "--invert-match")]
     args = [a for a in argv if not a.startswith("--")]
     flags = {a for a in argv if a.startswith("--")}
+    if patterns and flags & {"--count-lines", "--lines"} and not flags & {"--count", "--offsets"}:
+        if len(args) != 1 or len(flags) != 1:
+            raise SystemExit("./grep_hip.py (--count-lines | --lines) [-i] [-w | -x] [-v] [-A NUM] [-B NUM] [-C NUM] (-e <pattern>)... "
+                             "[-f <patterns file>] <file>")
+        if context and "--lines" not in flags:
+            raise SystemExit("./grep_hip.py: %s adds context LINES to the lines that --lines prints: it goes with --lines only; "
+                             "--count-lines prints a number" % context["flag"])
+        if word and line:
+            raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
+        if (word or line) and not all(patterns):
+            raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
+        if len(patterns) > ss.ANYOF_MAX_NEEDLES:
+            raise SystemExit("./grep_hip.py: %d patterns; a call takes %d (-e / -f)" % (len(patterns), ss.ANYOF_MAX_NEEDLES))
+        with ss.anyof_build():
+            searchers = [ss.DynamicHipSearcher.new_nocase(p) if fold else ss.DynamicHipSearcher.new(p) for p in patterns]
+        data = open(args[0], "rb").read()
+        if "--lines" in flags:
+            sys.stdout.buffer.write(context_lines(searchers, data, context.get("before", 0), context.get("after", 0), ignore_case=fold,
+                                                  invert=invert, whole_word=word, whole_line=line))
+        else:
+            print(ss.count_lines_anyof(searchers, data, ignore_case=fold, invert=invert, whole_word=word, whole_line=line))
+        return
     if patterns:
         if invert:
             raise SystemExit("./grep_hip.py: -v is not available with -e / -f: several patterns go through the batched library, which "
-                             "counts occurrences, and occurrences have no complement - run one pattern per call with --count-lines")
+                             "counts occurrences, and occurrences have no complement - run one pattern per call with --count-lines, or give --count-lines / --lines "
+                             "with the patterns (the lines that match none of them)")
         if word or line:
             raise SystemExit("./grep_hip.py: -w / -x are not available with -e / -f: several patterns go through the batched library, "
                              "which has no whole-word form - run one pattern per call")
