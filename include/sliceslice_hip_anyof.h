@@ -53,7 +53,7 @@
  * deterministic.  Rates measured on an MI355X are in DESIGN.md 5.13.
  *
  * Out of scope: ONE scan that filters for all needles in a single pass over the haystack (the follow-up that this header makes
- * measurable); async and capturable forms; batched, plan, sharded, service and host / file forms; -m; -o with several needles; a
+ * measurable: sliceslice_hip_needleset.h compiles the needles into a set and selects the same lines in one scan); async and capturable forms; batched, plan, sharded, service and host / file forms; -m; -o with several needles; a
  * `how` per needle; regular expressions; multi-byte terminators.
  */
 #ifndef SLICESLICE_HIP_ANYOF_H

@@ -40,7 +40,8 @@
  * Out of scope: the empty needle (GNU grep's answers for -w '' are a special case of its own); batched, plan, sharded, service and
  * host / file forms; early-exit search / find with bounds; Unicode or locale word classes; a caller-supplied byte class;
  * context lines and -m here.  (-v is sliceslice_hip_inverted.h's; context lines around the lines of these calls are
- * sliceslice_hip_context.h's; the lines that match any of several needles are sliceslice_hip_anyof.h's.)  Rates measured on an
+ * sliceslice_hip_context.h's; the lines that match any of several needles are sliceslice_hip_anyof.h's, in one scan for a compiled set
+ * sliceslice_hip_needleset.h's.)  Rates measured on an
  * MI355X are in DESIGN.md 5.10.
  */
 #ifndef SLICESLICE_HIP_BOUNDED_H

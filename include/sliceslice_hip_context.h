@@ -51,7 +51,7 @@
  *
  * Out of scope: -m; async and capturable forms; batched, plan, sharded, service and host / file forms; a form that never
  * materialises the selected numbers; several needles at once (-e A -e B, -f FILE: sliceslice_hip_anyof.h unites the numbers of
- * several needles' lines on the device and hands them to the primitive above); multi-byte terminators; regular expressions.
+ * several needles' lines on the device and hands them to the primitive above, sliceslice_hip_needleset.h finds them in one scan); multi-byte terminators; regular expressions.
  */
 #ifndef SLICESLICE_HIP_CONTEXT_H
 #define SLICESLICE_HIP_CONTEXT_H

@@ -42,7 +42,8 @@
  *
  * Out of scope: batched, plan, sharded, service and host / file forms; context lines (-A / -B / -C: they are
  * sliceslice_hip_context.h's, which takes these calls as models); several needles at once (-e A -e B, -f FILE: they are
- * sliceslice_hip_anyof.h's, whose SS_CONTEXT_INVERT selects the lines that match none of them); -m; the empty needle with -w / -x;
+ * sliceslice_hip_anyof.h's, whose SS_CONTEXT_INVERT selects the lines that match none of them, and in one scan for a whole set
+ * sliceslice_hip_needleset.h's); -m; the empty needle with -w / -x;
  * multi-byte terminators; regular expressions.
  */
 #ifndef SLICESLICE_HIP_INVERTED_H

@@ -164,6 +164,18 @@ ANYOF_ABI = {
 }
 ANYOF_MAX_NEEDLES = 65536           # SS_ANYOF_MAX_NEEDLES: needles (or lists) per call
 ANYOF_SEGMENT_LINES = 65536         # SS_ANYOF_SEGMENT_LINES: line numbers per workgroup of the union kernels
+# include/sliceslice_hip_needleset.h: the lines that match any of many needles in ONE pass over the haystack -
+# libsliceslice_hip_needleset.so only (the anyof library's objects plus the set scan)
+NEEDLESET_ABI = {
+    "ss_needle_set_new": (_int, [_vp, _vp, _u32, _uint, _pvp]),
+    "ss_needle_set_free": (None, [_vp]),
+    "ss_needle_set_info": (_int, [_vp, _vp]),
+    "ss_count_lines_set_device": (_int, [_vp, _vp, _sz, _int, _uint, _vp, _pu64]),
+    "ss_find_lines_set_device": (_int, [_vp, _vp, _sz, _int, _uint, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _pu64, _pu64]),
+}
+SS_SET_NOCASE = 1
+# ss_needle_set_stats: eight 64-bit words, in this order
+NEEDLESET_STATS = ("needles", "distinct", "blob_bytes", "one_byte", "two_byte", "prefix_keys", "largest_bucket", "fold")
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -256,7 +268,7 @@ def _bind(L, table, strict):
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
 # _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY and _build.NEXT_LIBRARY under their names, and the test hooks.
+# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY and _build.SET_LIBRARY under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -289,6 +301,9 @@ _FEATURES = {
     "anyof": (ANYOF_ABI, "ss_union_numbers_device",
               "the several-needle calls (count_lines_anyof / find_lines_anyof / union_numbers, grep -e A -e B) are not part of this "
               "library: they live in libsliceslice_hip_anyof.so - create the searchers inside `with ss.anyof_build():`"),
+    "needleset": (NEEDLESET_ABI, "ss_needle_set_new",
+                  "the needle-set calls (ss.NeedleSet: count_lines / find_lines for many needles in one pass, grep -f FILE) are not "
+                  "part of this library: they live in libsliceslice_hip_needleset.so - create the set inside `with ss.needleset_build():`"),
 }
 
 
@@ -335,7 +350,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY or _build.NEXT_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY or _build.SET_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -419,6 +434,15 @@ class anyof_build(_library_build):
     calls ``before`` / ``after`` - of searchers created inside the block, and ``ss.union_numbers`` / ``ss.union_numbers_into``, the
     ordered union of ascending lists of line numbers or its complement)."""
     name = "anyof"
+
+
+class needleset_build(_library_build):
+    """libsliceslice_hip_needleset.so: the anyof library plus the lines that match any of MANY needles, selected in ONE pass over
+    the haystack (include/sliceslice_hip_needleset.h: ``ss.NeedleSet(needles, ignore_case=False)`` with ``count_lines`` /
+    ``find_lines`` / ``find_lines_into`` / ``info`` - ``grep -e A -e B`` / ``grep -f FILE``; they take ``whole_word``,
+    ``whole_line`` and ``invert``, and the find calls ``before`` / ``after`` - of sets created inside the block; every anyof call
+    is there beside them for comparison)."""
+    name = "needleset"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -788,6 +812,86 @@ def union_numbers(lists, limit, complement=False, capacity=None, stream=None):
     out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
     total = union_numbers_into(lists, limit, out if capacity else None, capacity, complement, stream)
     return out[:min(int(capacity), total)]
+
+
+class NeedleSet:
+    """A compiled set of needles (ss_needle_set_new, inside ``with ss.needleset_build():``) on the current device.  Its line calls
+    select what ``ss.count_lines_anyof`` / ``ss.find_lines_anyof`` select for searchers of the same needles, in one pass over
+    the haystack instead of one per needle.  ``ignore_case`` is a property of the set: the needles are folded once, here."""
+
+    def __init__(self, needles, ignore_case=False):
+        self._h = None
+        self._L = L = _feature_lib(lib(), "needleset")
+        views = [_host_view(n.astype(np.uint8).tobytes() if isinstance(n, np.ndarray) else bytes(n)) for n in needles]
+        count = len(views)
+        table = (ctypes.c_void_p * max(count, 1))(*[v[1] if v[2] else None for v in views])
+        lens = (ctypes.c_size_t * max(count, 1))(*[v[2] for v in views])
+        h = ctypes.c_void_p()
+        _check(L.ss_needle_set_new(table, lens, count, SS_SET_NOCASE if ignore_case else 0, ctypes.byref(h)), L)
+        self._h = h
+        self.ignore_case = bool(ignore_case)
+
+    def _how(self, whole_word, whole_line, invert):
+        return _context_how(self.ignore_case, whole_word, whole_line, invert)
+
+    def info(self):
+        """dict of ss_needle_set_info: needles, distinct, blob_bytes, one_byte, two_byte, prefix_keys, largest_bucket, fold."""
+        words = (ctypes.c_uint64 * len(NEEDLESET_STATS))()
+        _check(self._L.ss_needle_set_info(self._h, words), self._L)
+        return dict(zip(NEEDLESET_STATS, (int(w) for w in words)))
+
+    def count_lines(self, haystack, delimiter=b"\n", whole_word=False, whole_line=False, invert=False, stream=None):
+        """The number of lines that hold ANY needle of the set (ss_count_lines_set_device); ``invert``: that hold none."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_lines_set_device(self._h, ptr, length, _delimiter_byte(delimiter), self._how(whole_word, whole_line, invert),
+                                                     st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", whole_word=False,
+                        whole_line=False, invert=False, stream=None):
+        """ss_find_lines_set_device into the caller's device tensors (8-byte x3, 1-byte kind; each may be None); returns
+        (total, selected)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total, selected = _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number, d_kind)]
+            _check(self._L.ss_find_lines_set_device(self._h, ptr, length, _delimiter_byte(delimiter), self._how(whole_word, whole_line, invert),
+                                                    _context_amount(before, "before"), _context_amount(after, "after"), st, p[0], p[1], p[2],
+                                                    p[3], int(capacity), ctypes.byref(total), ctypes.byref(selected)), self._L)
+        return total.value, selected.value
+
+    def find_lines(self, haystack, before=0, after=0, delimiter=b"\n", whole_word=False, whole_line=False, invert=False, capacity=None,
+                   stream=None):
+        """(begin, end, number, kind) of the selected lines with ``before`` / ``after`` context lines, every line once, ascending
+        (ss_find_lines_set_device); kind is 1 for a selected line and 0 for a context line."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        kw = dict(before=before, after=after, delimiter=delimiter, whole_word=whole_word, whole_line=whole_line, invert=invert, stream=stream)
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity, _ = self.find_lines_into(hay, None, None, None, None, 0, **kw)
+        out, kind = _context_arrays(capacity, dev)
+        p = [out[k] if capacity else None for k in range(3)] + [kind if capacity else None]
+        total, _ = self.find_lines_into(hay, p[0], p[1], p[2], p[3], capacity, **kw)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        L = getattr(self, "_L", None)
+        if h and L is not None and _lib is not None:
+            L.ss_needle_set_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DynamicHipSearcher:

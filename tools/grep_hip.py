@@ -29,7 +29,11 @@ the LINES that match ANY of the patterns (grep -e A -e B, grep -f FILE; -e may a
 number, --lines prints `number:line` for each - and, with -A / -B / -C (--lines only), the context lines as `number-line` and `--`
 between groups - byte for byte what `LC_ALL=C grep -F -c` / `LC_ALL=C grep -F -n` print (libsliceslice_hip_anyof.so,
 ss_count_lines_anyof_device / ss_find_lines_anyof_device: one searcher per pattern, the flags apply to every pattern; -v selects
-the lines that match none)."""
+the lines that match none).
+./grep_hip.py --one-pass (--count-lines | --lines) ... (-e <pattern>)... [-f <patterns file>] <file> - the same output, byte for byte,
+by ONE scan of the file for all patterns instead of one per pattern (libsliceslice_hip_needleset.so, ss_count_lines_set_device /
+ss_find_lines_set_device: the patterns are compiled into a set once).  --one-pass goes with -e / -f and --count-lines or --lines
+only; without it nothing changes."""
 import os
 import sys
 
@@ -86,7 +90,9 @@ def context_lines(searcher, data, before, after, ignore_case=False, invert=False
     printed lines, gathered on the device."""
     import torch
     hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
-    if isinstance(searcher, list):                              # several patterns: the lines that match any of them
+    if isinstance(searcher, ss.NeedleSet):                      # --one-pass: the fold is the set's
+        find = lambda *a, ignore_case=False, **kw: searcher.find_lines(*a, **kw)         # noqa: E731
+    elif isinstance(searcher, list):                            # several patterns: the lines that match any of them
         find = lambda *a, **kw: ss.find_lines_anyof(searcher, *a, **kw)                  # noqa: E731
     else:
         find = searcher.find_lines_context
@@ -133,6 +139,11 @@ def main():
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
     invert = "-v" in argv or "--invert-match" in argv
+    one_pass = "--one-pass" in argv
+    argv = [a for a in argv if a != "--one-pass"]
+    if one_pass and not (patterns and {"--count-lines", "--lines"} & set(argv) and not {"--count", "--offsets"} & set(argv)):
+        raise SystemExit("./grep_hip.py: --one-pass compiles several patterns into one set: it goes with -e / -f and --count-lines or "
+                         "--lines only")
     argv = [a for a in argv if a not in ("-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp", "-v", "--invert-match")]
     args = [a for a in argv if not a.startswith("--")]
     flags = {a for a in argv if a.startswith("--")}
@@ -149,6 +160,16 @@ def main():
             raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
         if len(patterns) > ss.ANYOF_MAX_NEEDLES:
             raise SystemExit("./grep_hip.py: %d patterns; a call takes %d (-e / -f)" % (len(patterns), ss.ANYOF_MAX_NEEDLES))
+        if one_pass:
+            with ss.needleset_build():
+                needles = ss.NeedleSet(patterns, ignore_case=fold)
+            data = open(args[0], "rb").read()
+            if "--lines" in flags:
+                sys.stdout.buffer.write(context_lines(needles, data, context.get("before", 0), context.get("after", 0), invert=invert,
+                                                      whole_word=word, whole_line=line))
+            else:
+                print(needles.count_lines(data, invert=invert, whole_word=word, whole_line=line))
+            return
         with ss.anyof_build():
             searchers = [ss.DynamicHipSearcher.new_nocase(p) if fold else ss.DynamicHipSearcher.new(p) for p in patterns]
         data = open(args[0], "rb").read()
