@@ -42,7 +42,8 @@
  * DESIGN.md 5.14.
  *
  * Out of scope: async and capturable forms; batched, plan, sharded, service and host / file forms; -m; -o; a `how` per needle;
- * regular expressions; multi-byte terminators; an occurrence (non-line) form for sets.
+ * regular expressions; multi-byte terminators; an occurrence (non-line) form for sets (sliceslice_hip_setmatches.h has it, in a
+ * library of its own).
  */
 #ifndef SLICESLICE_HIP_NEEDLESET_H
 #define SLICESLICE_HIP_NEEDLESET_H

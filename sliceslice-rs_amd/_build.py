@@ -3,7 +3,7 @@
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES, MORE_LIBRARIES and YET_MORE_LIBRARIES below (service, matches,
                                   matches_batched, lines, nocase; bounded; inverted), of ONE_MORE_LIBRARY (context), of
-                                  NEXT_LIBRARY (anyof) and of SET_LIBRARY (needleset): the
+                                  NEXT_LIBRARY (anyof), of SET_LIBRARY (needleset) and of OCCURRENCE_LIBRARY (setmatches): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -74,13 +74,17 @@ NEXT_LIBRARY = {
 SET_LIBRARY = {
     "needleset": _library("needleset", "anyof", ["ss_needleset.hip"]),
 }
+# A seventh table, again for the same reason: tests/test_needleset_cpu.py pins list(SET_LIBRARY) to ["needleset"].
+OCCURRENCE_LIBRARY = {
+    "setmatches": _library("setmatches", "needleset", ["ss_setmatches.hip"]),
+}
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
 _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
             "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "lines_scan_body.hpp", "lines_host.hpp", "matches_host.hpp",
             "scan_choice.hpp", "nocase_kernels.hpp", "nocase_launch.hpp", "bounded_kernels.hpp", "bounded_launch.hpp", "bounded_how.hpp",
-            "inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", "anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", "needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            "inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", "anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", "needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", "needleset_host.hpp", "setmatches_kernels.hpp", "setmatches_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_lines.h"),
@@ -90,6 +94,7 @@ _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_
             os.path.join("..", "..", "include", "sliceslice_hip_context.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_anyof.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_needleset.h"),
+            os.path.join("..", "..", "include", "sliceslice_hip_setmatches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_service.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_tuning.h")]
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden"]
@@ -256,8 +261,8 @@ def build(force=False, verbose=False):
 
 
 def _lib(name):
-    """The entry of library `name`, from whichever of the six tables holds it."""
-    for table in (LIBRARIES, MORE_LIBRARIES, YET_MORE_LIBRARIES, ONE_MORE_LIBRARY, NEXT_LIBRARY, SET_LIBRARY):
+    """The entry of library `name`, from whichever of the seven tables holds it."""
+    for table in (LIBRARIES, MORE_LIBRARIES, YET_MORE_LIBRARIES, ONE_MORE_LIBRARY, NEXT_LIBRARY, SET_LIBRARY, OCCURRENCE_LIBRARY):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -303,6 +308,7 @@ def build_inverted(force=False, verbose=False): return build_library("inverted",
 def build_context(force=False, verbose=False): return build_library("context", force, verbose)                    # noqa: E704
 def build_anyof(force=False, verbose=False): return build_library("anyof", force, verbose)                        # noqa: E704
 def build_needleset(force=False, verbose=False): return build_library("needleset", force, verbose)                # noqa: E704
+def build_setmatches(force=False, verbose=False): return build_library("setmatches", force, verbose)              # noqa: E704
 def service_library_path(): return library_path_of("service")                                                     # noqa: E704
 def matches_library_path(): return library_path_of("matches")                                                     # noqa: E704
 def matches_batched_library_path(): return library_path_of("matches_batched")                                     # noqa: E704
@@ -313,6 +319,7 @@ def inverted_library_path(): return library_path_of("inverted")                 
 def context_library_path(): return library_path_of("context")                                                     # noqa: E704
 def anyof_library_path(): return library_path_of("anyof")                                                         # noqa: E704
 def needleset_library_path(): return library_path_of("needleset")                                                 # noqa: E704
+def setmatches_library_path(): return library_path_of("setmatches")                                               # noqa: E704
 def matches_resources_path(): return LIBRARIES["matches"]["resources"]                                            # noqa: E704
 def matches_batched_resources_path(): return LIBRARIES["matches_batched"]["resources"]                            # noqa: E704
 def lines_resources_path(): return LIBRARIES["lines"]["resources"]                                                # noqa: E704
@@ -322,6 +329,7 @@ def inverted_resources_path(): return YET_MORE_LIBRARIES["inverted"]["resources"
 def context_resources_path(): return ONE_MORE_LIBRARY["context"]["resources"]                                     # noqa: E704
 def anyof_resources_path(): return NEXT_LIBRARY["anyof"]["resources"]                                             # noqa: E704
 def needleset_resources_path(): return SET_LIBRARY["needleset"]["resources"]                                      # noqa: E704
+def setmatches_resources_path(): return OCCURRENCE_LIBRARY["setmatches"]["resources"]                            # noqa: E704
 def matches_kernel_resources(): return library_kernel_resources("matches")                                        # noqa: E704
 def matches_batched_kernel_resources(): return library_kernel_resources("matches_batched")                        # noqa: E704
 def lines_kernel_resources(): return library_kernel_resources("lines")                                            # noqa: E704
@@ -332,6 +340,7 @@ def inverted_kernel_resources(): return library_kernel_resources("inverted")    
 def context_kernel_resources(): return library_kernel_resources("context")                                        # noqa: E704
 def anyof_kernel_resources(): return library_kernel_resources("anyof")                                            # noqa: E704
 def needleset_kernel_resources(): return library_kernel_resources("needleset")                                    # noqa: E704
+def setmatches_kernel_resources(): return library_kernel_resources("setmatches")                                  # noqa: E704
 
 
 def build_tools(force=False, verbose=False):

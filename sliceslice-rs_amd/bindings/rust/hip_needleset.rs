@@ -61,6 +61,11 @@ impl NeedleSet {
         NeedleSet { raw }
     }
 
+    /// The handle, for the calls of other modules that take a set (hip_setmatches.rs).
+    pub fn as_raw(&self) -> *const ss_needle_set {
+        self.raw
+    }
+
     pub fn info(&self) -> ss_needle_set_stats {
         let mut stats = ss_needle_set_stats::default();
         check(unsafe { ss_needle_set_info(self.raw, &mut stats) });

@@ -16,6 +16,7 @@
 #include "../../include/sliceslice_hip_needleset.h"
 #include "inverted_launch.hpp"
 #include "matches_scratch.hpp"
+#include "needleset_host.hpp"
 #include "needleset_kernels.hpp"
 
 #include <new>
@@ -40,14 +41,6 @@ hipError_t launch_set_scan(const SetArgs &sa, int mode, hipStream_t st)
 }
 
 }  // namespace ss
-
-struct ss_needle_set {
-    ss::SetTables host;
-    ss::SetView dev_view = {};
-    uint8_t *d_mem = nullptr;
-    int dev = -1;
-    ss_searcher *anchor = nullptr;          // names the device and its scratch for ss_lines_around_device; its needle is never looked at
-};
 
 namespace ssh {
 namespace {
@@ -284,7 +277,10 @@ int ss_needle_set_new(const void *const *needles, const size_t *lens, uint32_t c
     const ss::SetTables &t = set->host;
     const size_t o_bp = 0, o_b1 = o_bp + pad16(t.bp.size() * 4), o_bucket = o_b1 + pad16(t.b1.size() * 4),
                  o_entry = o_bucket + pad16(t.bucket.size() * 4), o_blob = o_entry + pad16(t.entry.size() * sizeof(ss::SetEntry)),
-                 size = o_blob + pad16(t.blob.size() + 1);
+                 o_rank1 = o_blob + pad16(t.blob.size() + 1), o_key2 = o_rank1 + pad16(t.rank1.size() * 4),
+                 o_rank2 = o_key2 + pad16(t.key2.size() * 4 + 4), o_erank = o_rank2 + pad16(t.rank2.size() * 4 + 4),
+                 o_slot = o_erank + pad16(t.erank.size() * 4 + 4), o_hot = o_slot + pad16(t.slot.size() * 4 + 4),
+                 size = o_hot + pad16(t.hot.size() * 4 + 4);
     const hipError_t e = hipMalloc(reinterpret_cast<void **>(&set->d_mem), size);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -296,6 +292,19 @@ int ss_needle_set_new(const void *const *needles, const size_t *lens, uint32_t c
     HIP_TRY(hipMemcpy(set->d_mem + o_bucket, t.bucket.data(), t.bucket.size() * 4, hipMemcpyHostToDevice));
     if (!t.entry.empty()) HIP_TRY(hipMemcpy(set->d_mem + o_entry, t.entry.data(), t.entry.size() * sizeof(ss::SetEntry), hipMemcpyHostToDevice));
     if (!t.blob.empty()) HIP_TRY(hipMemcpy(set->d_mem + o_blob, t.blob.data(), t.blob.size(), hipMemcpyHostToDevice));
+    // the side tables of needle identity (sliceslice_hip_setmatches.h), behind the blob
+    auto up = [&](size_t at, const std::vector<uint32_t> &v) {
+        return v.empty() ? hipSuccess : hipMemcpy(set->d_mem + at, v.data(), v.size() * 4, hipMemcpyHostToDevice);
+    };
+    HIP_TRY(up(o_rank1, t.rank1));
+    HIP_TRY(up(o_key2, t.key2));
+    HIP_TRY(up(o_rank2, t.rank2));
+    HIP_TRY(up(o_erank, t.erank));
+    HIP_TRY(up(o_slot, t.slot));
+    HIP_TRY(up(o_hot, t.hot));
+    auto words = [&](size_t at) { return reinterpret_cast<const uint32_t *>(set->d_mem + at); };
+    set->dev_ranks = ss::SetRanks{words(o_rank1), words(o_key2), words(o_rank2), words(o_erank), words(o_slot), words(o_hot),
+                                  (uint32_t)t.key2.size(), (uint32_t)t.hot.size()};
     set->dev_view = ss::SetView{reinterpret_cast<const uint32_t *>(set->d_mem + o_b1), reinterpret_cast<const uint32_t *>(set->d_mem + o_bp),
                                 reinterpret_cast<const uint32_t *>(set->d_mem + o_bucket), reinterpret_cast<const ss::SetEntry *>(set->d_mem + o_entry),
                                 set->d_mem + o_blob, t.fold, t.one_byte != 0 ? 1u : 0u};

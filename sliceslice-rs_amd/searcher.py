@@ -176,6 +176,14 @@ NEEDLESET_ABI = {
 SS_SET_NOCASE = 1
 # ss_needle_set_stats: eight 64-bit words, in this order
 NEEDLESET_STATS = ("needles", "distinct", "blob_bytes", "one_byte", "two_byte", "prefix_keys", "largest_bucket", "fold")
+# include/sliceslice_hip_setmatches.h: every occurrence of every needle of a set, counted per needle and listed as (offset, rank)
+# pairs in ONE pass - libsliceslice_hip_setmatches.so only (the needleset library's objects plus the occurrence scan)
+SETMATCHES_ABI = {
+    "ss_needle_set_ranks": (_int, [_vp, _vp]),
+    "ss_count_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _pu64]),
+    "ss_count_set_device_async": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _vp]),
+    "ss_find_all_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _vp, _u64, _pu64]),
+}
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -268,7 +276,7 @@ def _bind(L, table, strict):
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
 # _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY and _build.SET_LIBRARY under their names, and the test hooks.
+# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY and _build.OCCURRENCE_LIBRARY under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -304,6 +312,10 @@ _FEATURES = {
     "needleset": (NEEDLESET_ABI, "ss_needle_set_new",
                   "the needle-set calls (ss.NeedleSet: count_lines / find_lines for many needles in one pass, grep -f FILE) are not "
                   "part of this library: they live in libsliceslice_hip_needleset.so - create the set inside `with ss.needleset_build():`"),
+    "setmatches": (SETMATCHES_ABI, "ss_count_set_device",
+                   "the occurrence calls of a needle set (ss.NeedleSet: ranks / count / count_total / count_async / find_all / "
+                   "find_all_into) are not part of this library: they live in libsliceslice_hip_setmatches.so - create the set "
+                   "inside `with ss.setmatches_build():`"),
 }
 
 
@@ -350,7 +362,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY or _build.SET_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY or _build.OCCURRENCE_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -443,6 +455,14 @@ class needleset_build(_library_build):
     ``whole_line`` and ``invert``, and the find calls ``before`` / ``after`` - of sets created inside the block; every anyof call
     is there beside them for comparison)."""
     name = "needleset"
+
+
+class setmatches_build(_library_build):
+    """libsliceslice_hip_setmatches.so: the needleset library plus every occurrence of every needle of a set in ONE pass over the
+    haystack (include/sliceslice_hip_setmatches.h: ``ranks`` / ``count`` / ``count_total`` / ``count_async`` / ``find_all`` /
+    ``find_all_into`` of ``ss.NeedleSet`` objects created inside the block - a word-frequency table and the ascending
+    (offset, needle) pairs; they take ``whole_word``)."""
+    name = "setmatches"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -829,6 +849,7 @@ class NeedleSet:
         h = ctypes.c_void_p()
         _check(L.ss_needle_set_new(table, lens, count, SS_SET_NOCASE if ignore_case else 0, ctypes.byref(h)), L)
         self._h = h
+        self._count = count
         self.ignore_case = bool(ignore_case)
 
     def _how(self, whole_word, whole_line, invert):
@@ -880,6 +901,99 @@ class NeedleSet:
         total, _ = self.find_lines_into(hay, p[0], p[1], p[2], p[3], capacity, **kw)
         k = min(int(capacity), total)
         return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+    # -- every occurrence, per needle (include/sliceslice_hip_setmatches.h; inside ``with ss.setmatches_build():``) --------------
+    def _occurrence_how(self, whole_word):
+        return (SS_BOUND_WORD if whole_word else 0) | (SS_BOUND_NOCASE if self.ignore_case else 0)
+
+    def ranks(self):
+        """The rank of every needle as given (ss_needle_set_ranks): its position in the set's sorted, deduplicated order, as an
+        int64 numpy array; duplicates and needles equal after the fold share a rank."""
+        L = _feature_lib(self._L, "setmatches")
+        if getattr(self, "_ranks", None) is None:
+            out = np.zeros(max(self._count, 1), dtype=np.uint32)
+            _check(L.ss_needle_set_ranks(self._h, out.ctypes.data), L)
+            self._ranks = out[:self._count].astype(np.int64)
+        return self._ranks
+
+    def _rank_maps(self, dev):
+        """(ranks, the smallest given index of every rank) as int64 tensors on `dev`."""
+        import torch
+        maps = self.__dict__.setdefault("_maps", {})
+        if dev not in maps:
+            ranks = self.ranks()
+            first = np.full(int(ranks.max()) + 1 if len(ranks) else 0, len(ranks), dtype=np.int64)
+            np.minimum.at(first, ranks, np.arange(len(ranks), dtype=np.int64))
+            maps[dev] = (torch.from_numpy(ranks).to(dev), torch.from_numpy(first).to(dev))
+        return maps[dev]
+
+    def count_async(self, haystack, d_counts, d_total, whole_word=False, stream=None):
+        """ss_count_set_device_async into the caller's 8-byte device tensors: ``d_counts`` in RANK space (``info()["distinct"]``
+        entries) and ``d_total`` (one entry); either may be None, not both.  Stream-ordered and capturable."""
+        L = _feature_lib(self._L, "setmatches")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_count_set_device_async(self._h, ptr, length, self._occurrence_how(whole_word), st,
+                                               d_counts.data_ptr() if d_counts is not None else None,
+                                               d_total.data_ptr() if d_total is not None else None), L)
+
+    def _count_ranks(self, haystack, d_counts, whole_word, stream):
+        L = _feature_lib(self._L, "setmatches")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_count_set_device(self._h, ptr, length, self._occurrence_how(whole_word), st,
+                                         d_counts.data_ptr() if d_counts is not None else None, ctypes.byref(total)), L)
+        return total.value
+
+    def count(self, haystack, whole_word=False, stream=None):
+        """The occurrences of every needle AS GIVEN, overlapping ones included, as an int64 device tensor (ss_count_set_device: the
+        counts per rank, gathered through ``ranks()``; duplicates show equal values) - what ``count`` of a searcher of each
+        needle returns on the same haystack."""
+        import torch
+        _feature_lib(self._L, "setmatches")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        ranks, first = self._rank_maps(dev)
+        by_rank = torch.empty(max(first.numel(), 1), dtype=torch.int64, device=dev)
+        self._count_ranks(t if t is not None else (ptr, length), by_rank, whole_word, stream)
+        return by_rank[ranks]
+
+    def count_total(self, haystack, whole_word=False, stream=None):
+        """The number of (offset, needle) pairs: the sum of the counts of the DISTINCT needles (ss_count_set_device without bins)."""
+        _feature_lib(self._L, "setmatches")
+        return self._count_ranks(haystack, None, whole_word, stream)
+
+    def find_all_into(self, haystack, d_offsets, d_ranks, capacity, whole_word=False, stream=None):
+        """ss_find_all_set_device into the caller's device tensors (8-byte offsets, 4-byte RANKS; each may be None); returns the
+        total number of pairs."""
+        L = _feature_lib(self._L, "setmatches")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_find_all_set_device(self._h, ptr, length, self._occurrence_how(whole_word), st,
+                                            d_offsets.data_ptr() if d_offsets is not None else None,
+                                            d_ranks.data_ptr() if d_ranks is not None else None, int(capacity), ctypes.byref(total)), L)
+        return total.value
+
+    def find_all(self, haystack, whole_word=False, capacity=None, stream=None):
+        """(offsets, needle_index) of the first ``capacity`` (default: all) occurrences of the set's needles, ordered by offset and
+        then by rank, as int64 device tensors; ``needle_index`` is the smallest index as given of the needle of that rank."""
+        import torch
+        _feature_lib(self._L, "setmatches")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.find_all_into(hay, None, None, 0, whole_word, stream)
+        offsets = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        rank = torch.empty(max(int(capacity), 1), dtype=torch.int32, device=dev)
+        total = self.find_all_into(hay, offsets if capacity else None, rank if capacity else None, capacity, whole_word, stream)
+        k = min(int(capacity), total)
+        return offsets[:k], self._rank_maps(dev)[1][rank[:k].long()]
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

@@ -33,7 +33,12 @@ the lines that match none).
 ./grep_hip.py --one-pass (--count-lines | --lines) ... (-e <pattern>)... [-f <patterns file>] <file> - the same output, byte for byte,
 by ONE scan of the file for all patterns instead of one per pattern (libsliceslice_hip_needleset.so, ss_count_lines_set_device /
 ss_find_lines_set_device: the patterns are compiled into a set once).  --one-pass goes with -e / -f and --count-lines or --lines
-only; without it nothing changes."""
+only; without it nothing changes.
+./grep_hip.py --frequencies [-i] [-w] (-e <pattern>)... [-f <patterns file>] <file> - a word-frequency table: one count of
+(overlapping) OCCURRENCES per pattern and line, in the order given, from ONE scan of the file for all patterns
+(libsliceslice_hip_setmatches.so, ss_count_set_device: the patterns are compiled into a set once, and the counts per distinct
+pattern are gathered back into the order given).  Without -i / -w the output is byte for byte what --count -e ... prints.  -x, -v
+and -A / -B / -C are refused: occurrences know no line, have no complement and no context; so is the empty pattern."""
 import os
 import sys
 
@@ -139,6 +144,25 @@ def main():
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
     invert = "-v" in argv or "--invert-match" in argv
+    if "--frequencies" in argv:
+        rest = [a for a in argv if a not in ("--frequencies", "-i", "--ignore-case", "-w", "--word-regexp")]
+        if line:
+            raise SystemExit("./grep_hip.py: -x is about lines, and --frequencies counts occurrences, which know no line")
+        if invert:
+            raise SystemExit("./grep_hip.py: -v is about lines: --frequencies counts occurrences, which have no complement")
+        if context:
+            raise SystemExit("./grep_hip.py: %s adds context LINES: --frequencies counts occurrences and prints numbers" % context["flag"])
+        if not patterns or len(rest) != 1 or rest[0].startswith("--"):
+            raise SystemExit("./grep_hip.py --frequencies [-i] [-w] (-e <pattern>)... [-f <patterns file>] <file>")
+        if not all(patterns):
+            raise SystemExit("./grep_hip.py: --frequencies with the empty pattern is out of scope (its occurrences belong to no scan)")
+        if len(patterns) > ss.ANYOF_MAX_NEEDLES:
+            raise SystemExit("./grep_hip.py: %d patterns; a set takes %d (-e / -f)" % (len(patterns), ss.ANYOF_MAX_NEEDLES))
+        with ss.setmatches_build():
+            needles = ss.NeedleSet(patterns, ignore_case=fold)
+        data = open(rest[0], "rb").read()
+        sys.stdout.write("".join("%d\n" % c for c in needles.count(data, whole_word=word).cpu().tolist()))
+        return
     one_pass = "--one-pass" in argv
     argv = [a for a in argv if a != "--one-pass"]
     if one_pass and not (patterns and {"--count-lines", "--lines"} & set(argv) and not {"--count", "--offsets"} & set(argv)):
