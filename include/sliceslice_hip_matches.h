@@ -11,7 +11,8 @@
  * Occurrences are OVERLAPPING: every offset i with haystack[i .. i+n) == needle ("aa" in "aaaa": 3, at 0, 1, 2).
  * Empty needle: len + 1 occurrences at 0 .. len (Python's bytes.count, memchr's find_iter).  n > len: 0.
  * Non-overlapping counts (bytes.count's rule for needles that overlap themselves) follow from the offsets on the host: walk them
- * in order and keep an offset when it is at least n past the last one kept.
+ * in order and keep an offset when it is at least n past the last one kept.  (That walk, on the device, and the replacement of the
+ * occurrences it keeps are sliceslice_hip_disjoint.h's.)
  *
  * Argument checks, error codes and ss_last_error follow ss_find_device; the calls work for every searcher the constructors and
  * ss_searcher_set_filter3 can make, and offsets are 64-bit (haystacks above 4 GiB included).  The calls neither start nor read the

@@ -40,7 +40,8 @@
  * of the first `capacity` pairs; no sort.  Design and measurements: DESIGN.md 5.15.
  *
  * Out of scope: the empty needle; SS_BOUND_LINE and inverted forms; leftmost-longest / non-overlapping selection (it follows on
- * the host from the ordered pairs); batched, plan, sharded, service and host / file forms.
+ * the host from the ordered pairs); batched, plan, sharded, service and host / file forms.  (The non-overlapping occurrences of ONE
+ * needle are sliceslice_hip_disjoint.h's; its primitive takes one length, so it does not select among a set's pairs.)
  */
 #ifndef SLICESLICE_HIP_SETMATCHES_H
 #define SLICESLICE_HIP_SETMATCHES_H

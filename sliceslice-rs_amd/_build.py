@@ -3,7 +3,8 @@
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES, MORE_LIBRARIES and YET_MORE_LIBRARIES below (service, matches,
                                   matches_batched, lines, nocase; bounded; inverted), of ONE_MORE_LIBRARY (context), of
-                                  NEXT_LIBRARY (anyof), of SET_LIBRARY (needleset) and of OCCURRENCE_LIBRARY (setmatches): the
+                                  NEXT_LIBRARY (anyof), of SET_LIBRARY (needleset), of OCCURRENCE_LIBRARY (setmatches) and of DISJOINT_LIBRARY
+                                  (disjoint): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -78,13 +79,17 @@ SET_LIBRARY = {
 OCCURRENCE_LIBRARY = {
     "setmatches": _library("setmatches", "needleset", ["ss_setmatches.hip"]),
 }
+# An eighth table, again for the same reason: tests/test_setmatches_cpu.py pins list(OCCURRENCE_LIBRARY) to ["setmatches"].
+DISJOINT_LIBRARY = {
+    "disjoint": _library("disjoint", "setmatches", ["ss_disjoint.hip"]),
+}
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
 _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
             "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "lines_scan_body.hpp", "lines_host.hpp", "matches_host.hpp",
             "scan_choice.hpp", "nocase_kernels.hpp", "nocase_launch.hpp", "bounded_kernels.hpp", "bounded_launch.hpp", "bounded_how.hpp",
-            "inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", "anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", "needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", "needleset_host.hpp", "setmatches_kernels.hpp", "setmatches_launch.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
+            "inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", "anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", "needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", "needleset_host.hpp", "setmatches_kernels.hpp", "setmatches_launch.hpp", "disjoint_kernels.hpp", "disjoint_launch.hpp", "disjoint_host.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_lines.h"),
@@ -95,6 +100,7 @@ _HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_
             os.path.join("..", "..", "include", "sliceslice_hip_anyof.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_needleset.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_setmatches.h"),
+            os.path.join("..", "..", "include", "sliceslice_hip_disjoint.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_service.h"),
             os.path.join("..", "..", "include", "sliceslice_hip_tuning.h")]
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden"]
@@ -261,8 +267,8 @@ def build(force=False, verbose=False):
 
 
 def _lib(name):
-    """The entry of library `name`, from whichever of the seven tables holds it."""
-    for table in (LIBRARIES, MORE_LIBRARIES, YET_MORE_LIBRARIES, ONE_MORE_LIBRARY, NEXT_LIBRARY, SET_LIBRARY, OCCURRENCE_LIBRARY):
+    """The entry of library `name`, from whichever of the eight tables holds it."""
+    for table in (LIBRARIES, MORE_LIBRARIES, YET_MORE_LIBRARIES, ONE_MORE_LIBRARY, NEXT_LIBRARY, SET_LIBRARY, OCCURRENCE_LIBRARY, DISJOINT_LIBRARY):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -309,6 +315,7 @@ def build_context(force=False, verbose=False): return build_library("context", f
 def build_anyof(force=False, verbose=False): return build_library("anyof", force, verbose)                        # noqa: E704
 def build_needleset(force=False, verbose=False): return build_library("needleset", force, verbose)                # noqa: E704
 def build_setmatches(force=False, verbose=False): return build_library("setmatches", force, verbose)              # noqa: E704
+def build_disjoint(force=False, verbose=False): return build_library("disjoint", force, verbose)                  # noqa: E704
 def service_library_path(): return library_path_of("service")                                                     # noqa: E704
 def matches_library_path(): return library_path_of("matches")                                                     # noqa: E704
 def matches_batched_library_path(): return library_path_of("matches_batched")                                     # noqa: E704
@@ -320,6 +327,7 @@ def context_library_path(): return library_path_of("context")                   
 def anyof_library_path(): return library_path_of("anyof")                                                         # noqa: E704
 def needleset_library_path(): return library_path_of("needleset")                                                 # noqa: E704
 def setmatches_library_path(): return library_path_of("setmatches")                                               # noqa: E704
+def disjoint_library_path(): return library_path_of("disjoint")                                                   # noqa: E704
 def matches_resources_path(): return LIBRARIES["matches"]["resources"]                                            # noqa: E704
 def matches_batched_resources_path(): return LIBRARIES["matches_batched"]["resources"]                            # noqa: E704
 def lines_resources_path(): return LIBRARIES["lines"]["resources"]                                                # noqa: E704
@@ -330,6 +338,7 @@ def context_resources_path(): return ONE_MORE_LIBRARY["context"]["resources"]   
 def anyof_resources_path(): return NEXT_LIBRARY["anyof"]["resources"]                                             # noqa: E704
 def needleset_resources_path(): return SET_LIBRARY["needleset"]["resources"]                                      # noqa: E704
 def setmatches_resources_path(): return OCCURRENCE_LIBRARY["setmatches"]["resources"]                            # noqa: E704
+def disjoint_resources_path(): return DISJOINT_LIBRARY["disjoint"]["resources"]                                  # noqa: E704
 def matches_kernel_resources(): return library_kernel_resources("matches")                                        # noqa: E704
 def matches_batched_kernel_resources(): return library_kernel_resources("matches_batched")                        # noqa: E704
 def lines_kernel_resources(): return library_kernel_resources("lines")                                            # noqa: E704
@@ -341,6 +350,7 @@ def context_kernel_resources(): return library_kernel_resources("context")      
 def anyof_kernel_resources(): return library_kernel_resources("anyof")                                            # noqa: E704
 def needleset_kernel_resources(): return library_kernel_resources("needleset")                                    # noqa: E704
 def setmatches_kernel_resources(): return library_kernel_resources("setmatches")                                  # noqa: E704
+def disjoint_kernel_resources(): return library_kernel_resources("disjoint")                                      # noqa: E704
 
 
 def build_tools(force=False, verbose=False):

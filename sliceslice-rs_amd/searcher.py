@@ -184,6 +184,16 @@ SETMATCHES_ABI = {
     "ss_count_set_device_async": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _vp]),
     "ss_find_all_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _vp, _u64, _pu64]),
 }
+# include/sliceslice_hip_disjoint.h: the non-overlapping occurrences of a needle (count, offsets, replace) and the greedy selection
+# over any ascending list of offsets - libsliceslice_hip_disjoint.so only (the setmatches library's objects plus the selection and
+# the replace kernels)
+DISJOINT_ABI = {
+    "ss_select_disjoint_device": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, _u64, _pu64]),
+    "ss_count_disjoint_device": (_int, [_vp, _vp, _sz, _uint, _vp, _pu64]),
+    "ss_find_all_disjoint_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _u64, _pu64]),
+    "ss_replace_device": (_int, [_vp, _vp, _sz, _uint, _vp, _sz, _vp, _vp, _u64, _pu64, _pu64]),
+}
+DISJOINT_BLOCK = 4096               # SS_DISJOINT_BLOCK: offsets per workgroup of the selection kernels
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -276,7 +286,7 @@ def _bind(L, table, strict):
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
 # _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY and _build.OCCURRENCE_LIBRARY under their names, and the test hooks.
+# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY, _build.OCCURRENCE_LIBRARY and _build.DISJOINT_LIBRARY under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -316,6 +326,10 @@ _FEATURES = {
                    "the occurrence calls of a needle set (ss.NeedleSet: ranks / count / count_total / count_async / find_all / "
                    "find_all_into) are not part of this library: they live in libsliceslice_hip_setmatches.so - create the set "
                    "inside `with ss.setmatches_build():`"),
+    "disjoint": (DISJOINT_ABI, "ss_count_disjoint_device",
+                 "the non-overlapping calls (count_disjoint / find_all_disjoint / find_all_disjoint_into / replace / "
+                 "select_disjoint / select_disjoint_into) are not part of this library: they live in "
+                 "libsliceslice_hip_disjoint.so - create the searcher inside `with ss.disjoint_build():`"),
 }
 
 
@@ -362,7 +376,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY or _build.OCCURRENCE_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY, _build.OCCURRENCE_LIBRARY or _build.DISJOINT_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None
@@ -463,6 +477,15 @@ class setmatches_build(_library_build):
     ``find_all_into`` of ``ss.NeedleSet`` objects created inside the block - a word-frequency table and the ascending
     (offset, needle) pairs; they take ``whole_word``)."""
     name = "setmatches"
+
+
+class disjoint_build(_library_build):
+    """libsliceslice_hip_disjoint.so: the setmatches library plus the NON-OVERLAPPING occurrences of a needle
+    (include/sliceslice_hip_disjoint.h: ``count_disjoint`` / ``find_all_disjoint`` / ``find_all_disjoint_into`` / ``replace`` of
+    searchers created inside the block - ``bytes.count``, ``grep -o``, ``bytes.replace``; they take ``ignore_case`` and
+    ``whole_word`` - and ``ss.select_disjoint`` / ``ss.select_disjoint_into``, the greedy selection over any ascending list of
+    offsets)."""
+    name = "disjoint"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -834,6 +857,38 @@ def union_numbers(lists, limit, complement=False, capacity=None, stream=None):
     return out[:min(int(capacity), total)]
 
 
+def select_disjoint_into(offsets, n, d_out, stream=None):
+    """ss_select_disjoint_device into the caller's 8-byte device tensor (capacity = its length; None: count only); returns the size
+    of the selection.  Inside ``with ss.disjoint_build():``."""
+    import torch
+    L = _feature_lib(lib(), "disjoint")
+    dev = offsets.device if _is_tensor(offsets) and offsets.is_cuda else (d_out.device if d_out is not None else torch.device("cuda", torch.cuda.current_device()))
+    s = _UNION_SEARCHERS.get(id(L)) or _UNION_SEARCHERS.setdefault(id(L), DynamicHipSearcher.new(b""))     # (for the device and its scratch only)
+    total = _u64(0)
+    with _on_device_of(d_out if d_out is not None else offsets):
+        flat = _device_numbers(offsets, dev).reshape(-1)
+        st = stream if stream is not None else _current_stream_handle()
+        _check(L.ss_select_disjoint_device(s._h, flat.data_ptr() if flat.numel() else None, flat.numel(), int(n), st,
+                                           d_out.data_ptr() if d_out is not None and d_out.numel() else None,
+                                           d_out.numel() if d_out is not None else 0, ctypes.byref(total)), L)
+    return total.value
+
+
+def select_disjoint(offsets, n, capacity=None, stream=None):
+    """The greedy non-overlapping selection over the strictly ascending ``offsets`` (a sequence, an array or a device tensor) of
+    occurrences of length ``n``: the first is selected, and after a selected p the first at or beyond p + n - as an int64 device
+    tensor of min(total, capacity) offsets (ss_select_disjoint_device).  Inside ``with ss.disjoint_build():``."""
+    import torch
+    _feature_lib(lib(), "disjoint")
+    dev = offsets.device if _is_tensor(offsets) and offsets.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    flat = _device_numbers(offsets, dev).reshape(-1)
+    if capacity is None:
+        capacity = select_disjoint_into(flat, n, None, stream)
+    out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+    total = select_disjoint_into(flat, n, out[:int(capacity)] if capacity else None, stream)
+    return out[:min(int(capacity), total)]
+
+
 class NeedleSet:
     """A compiled set of needles (ss_needle_set_new, inside ``with ss.needleset_build():``) on the current device.  Its line calls
     select what ``ss.count_lines_anyof`` / ``ss.find_lines_anyof`` select for searchers of the same needles, in one pass over
@@ -1170,6 +1225,67 @@ class DynamicHipSearcher:
             st = stream if stream is not None else _current_stream_handle()
             self._ck(fn(self._h, ptr, length, st, d_offsets.data_ptr() if d_offsets.numel() else None, d_offsets.numel(), ctypes.byref(total)))
         return total.value
+
+    # -- the non-overlapping occurrences (libsliceslice_hip_disjoint.so: searchers made inside `with ss.disjoint_build():`) ------
+    @staticmethod
+    def _disjoint_how(ignore_case, whole_word):
+        return (SS_BOUND_WORD if whole_word else 0) | (SS_BOUND_NOCASE if ignore_case else 0)
+
+    def count_disjoint(self, haystack, stream=None, ignore_case=False, whole_word=False):
+        """int: the number of NON-OVERLAPPING occurrences of the needle, taken greedily from the left - ``bytes.count``
+        (ss_count_disjoint_device).  ignore_case / whole_word as in ``count``; the bounds test comes before the selection."""
+        L = _feature_lib(self._L, "disjoint")
+        ptr, length, t = self._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_count_disjoint_device(self._h, ptr, length, self._disjoint_how(ignore_case, whole_word), st, ctypes.byref(c)))
+        return c.value
+
+    def find_all_disjoint_into(self, haystack, d_offsets, stream=None, ignore_case=False, whole_word=False):
+        """ss_find_all_disjoint_device into a caller's 8-byte device tensor (capacity = its length); returns the total count."""
+        L = _feature_lib(self._L, "disjoint")
+        ptr, length, t = self._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_find_all_disjoint_device(self._h, ptr, length, self._disjoint_how(ignore_case, whole_word), st,
+                                                   d_offsets.data_ptr() if d_offsets.numel() else None, d_offsets.numel(), ctypes.byref(total)))
+        return total.value
+
+    def find_all_disjoint(self, haystack, capacity=None, stream=None, ignore_case=False, whole_word=False):
+        """int64 tensor on the haystack's device: the offsets of the non-overlapping occurrences in ascending order - what
+        ``grep -o -b`` prints (ss_find_all_disjoint_device).  capacity=None: counted first, then exactly that many; else the leftmost
+        ``capacity`` of them."""
+        import torch
+        _feature_lib(self._L, "disjoint")
+        ptr, length, t = self._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.count_disjoint(hay, stream, ignore_case, whole_word)
+        out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        total = self.find_all_disjoint_into(hay, out[:int(capacity)], stream, ignore_case, whole_word)
+        return out[:min(int(capacity), total)]
+
+    def replace(self, haystack, replacement, stream=None, ignore_case=False, whole_word=False):
+        """uint8 tensor on the haystack's device: the haystack with every non-overlapping occurrence of the needle replaced by
+        ``replacement`` (host bytes, may be empty) - ``bytes.replace`` (ss_replace_device; sized with the count first)."""
+        import torch
+        L = _feature_lib(self._L, "disjoint")
+        ptr, length, t = self._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        rep = bytes(replacement)
+        keep, addr, rn = _host_view(rep)
+        how = self._disjoint_how(ignore_case, whole_word)
+        out_len, c = _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_replace_device(self._h, ptr, length, how, addr, rn, st, None, 0, ctypes.byref(out_len), ctypes.byref(c)))
+            out = torch.empty(max(out_len.value, 1), dtype=torch.uint8, device=dev)
+            if out_len.value:
+                self._ck(L.ss_replace_device(self._h, ptr, length, how, addr, rn, st, out.data_ptr(), out_len.value, ctypes.byref(out_len), ctypes.byref(c)))
+        return out[:min(out_len.value, out.numel() if out_len.value else 0)]
 
     # -- the lines that contain the needle (libsliceslice_hip_lines.so: searchers made inside `with ss.lines_build():`) ------
     def count_lines(self, haystack, delimiter=b"\n", stream=None, ignore_case=False, whole_word=False, whole_line=False):

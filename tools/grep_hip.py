@@ -38,7 +38,15 @@ only; without it nothing changes.
 (overlapping) OCCURRENCES per pattern and line, in the order given, from ONE scan of the file for all patterns
 (libsliceslice_hip_setmatches.so, ss_count_set_device: the patterns are compiled into a set once, and the counts per distinct
 pattern are gathered back into the order given).  Without -i / -w the output is byte for byte what --count -e ... prints.  -x, -v
-and -A / -B / -C are refused: occurrences know no line, have no complement and no context; so is the empty pattern."""
+and -A / -B / -C are refused: occurrences know no line, have no complement and no context; so is the empty pattern.
+./grep_hip.py -o (--count | --offsets) [-i] [-w] <needle> <file> - the NON-OVERLAPPING occurrences, taken greedily from the left
+(-o, --only-matching; libsliceslice_hip_disjoint.so, ss_count_disjoint_device / ss_find_all_disjoint_device): --count prints their
+number (bytes.count), --offsets prints `offset:match` for each, byte for byte what grep -o -b -F prints (with -i the match is the
+file's own bytes).  Without -o, --count and --offsets stay what they were: every overlapping occurrence.
+./grep_hip.py --replace <text> [-i] [-w] <needle> <file> - the file with every non-overlapping occurrence replaced by <text>, to
+stdout (sed 's/needle/text/g' for a fixed string, bytes.replace; ss_replace_device: the substituted bytes are made on the device).
+Both refuse -x, -v, -A / -B / -C, --count-lines, --lines, --frequencies and -e / -f: the non-overlapping selection is about the
+occurrences of one needle; --replace refuses the empty needle."""
 import os
 import sys
 
@@ -119,10 +127,13 @@ def context_lines(searcher, data, before, after, ignore_case=False, invert=False
 
 
 def main():
-    argv, patterns, context = [], [], {}
+    argv, patterns, context, replacement = [], [], {}, None
     it = iter(sys.argv[1:])
     for a in it:
-        if a == "-e":
+        if a == "--replace":
+            argv.append(a)
+            replacement = next(it, None)
+        elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
             patterns += [l for l in open(next(it), "rb").read().split(b"\n") if l]
@@ -144,6 +155,39 @@ def main():
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
     invert = "-v" in argv or "--invert-match" in argv
+    only = "-o" in argv or "--only-matching" in argv
+    if only or "--replace" in argv:
+        what = "--replace" if "--replace" in argv else "-o"
+        usage = ("./grep_hip.py -o (--count | --offsets) [-i] [-w] <needle> <file>\n"
+                 "./grep_hip.py --replace <text> [-i] [-w] <needle> <file>")
+        refused = [("-x", line), ("-v", invert), (context.get("flag"), bool(context))] + \
+                  [(f, f in argv) for f in ("--count-lines", "--lines", "--frequencies", "--one-pass")] + [("-e / -f", bool(patterns))] + \
+                  [(f, f in argv and what == "--replace") for f in ("--count", "--offsets", "-o", "--only-matching")]
+        for flag, given in refused:
+            if given:
+                raise SystemExit("./grep_hip.py: %s does not go with %s: the non-overlapping selection is about the occurrences of one "
+                                 "needle (-i and -w combine with it)" % (flag, what))
+        rest = [a for a in argv if a not in ("-o", "--only-matching", "--replace", "-i", "--ignore-case", "-w", "--word-regexp")]
+        args, flags = [a for a in rest if not a.startswith("--")], {a for a in rest if a.startswith("--")}
+        if len(args) != 2 or (what == "--replace" and (replacement is None or flags)) or (what == "-o" and flags not in ({"--count"}, {"--offsets"})):
+            raise SystemExit(usage)
+        needle = args[0].encode()
+        if not needle and (what == "--replace" or fold or word):
+            raise SystemExit("./grep_hip.py: the empty needle cannot be replaced, folded or stand as a word (non-overlapping forms)")
+        with ss.disjoint_build():
+            searcher = ss.DynamicHipSearcher.new_nocase(needle) if fold else ss.DynamicHipSearcher.new(needle)
+        import torch
+        data = open(args[1], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        if what == "--replace":
+            sys.stdout.buffer.write(searcher.replace(hay, replacement.encode(), ignore_case=fold, whole_word=word).cpu().numpy().tobytes())
+        elif "--count" in flags:
+            print(searcher.count_disjoint(hay, ignore_case=fold, whole_word=word))
+        else:
+            n = len(needle)
+            sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (o, data[o:o + n])
+                                             for o in searcher.find_all_disjoint(hay, ignore_case=fold, whole_word=word).cpu().tolist()))
+        return
     if "--frequencies" in argv:
         rest = [a for a in argv if a not in ("--frequencies", "-i", "--ignore-case", "-w", "--word-regexp")]
         if line:
