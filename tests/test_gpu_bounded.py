@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_matches import _loaded, kernel_of, ref_offsets
+from test_gpu_matches import _loaded, kernel_of, n_tiles, ref_offsets, tiles_per_workgroup
 
 pytestmark = pytest.mark.gpu
 
@@ -525,8 +525,8 @@ def test_every_refusal_writes_nothing(ss):
         s.count_lines(d, 256, whole_word=True)
 
 
-def test_a_large_haystack_two_tiles_per_workgroup(ss):
-    n_bytes = 160 * MiB                                     # (the size tests/test_gpu_nocase.py uses for its two-tile grids)
+def test_a_160_mib_haystack_of_40_chunks_at_one_tile_per_workgroup(ss):
+    n_bytes = 160 * MiB                                     # (one tile per workgroup; the size of tests/test_gpu_nocase.py's test of this name)
     hay = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
     ss.fill_random_device(hay, 0x0B0D)
     hay.masked_fill_(hay == ord("Q"), ord("r"))
@@ -534,6 +534,12 @@ def test_a_large_haystack_two_tiles_per_workgroup(ss):
     rng = np.random.default_rng(76)
     needle = b"quite a long needle, 33 bytes: qz"
     s, s2 = make(ss, needle), make(ss, b"qz")
+    # the shape this size really has (the launch rules as tests/test_gpu_matches.py restates them): 10,240 tiles, ONE per workgroup
+    # - two begin at 2 * CUs * 256 tiles, 2 GiB on 256 CUs - and 10,242 parts, so lines_chunk_kernel has 40 full chunks and the
+    # combine walks them.  Two-tile grids, chunk borders on purpose and runs of chunks: tests/test_gpu_lines_grids.py.
+    cus = ss.device_info()["compute_units"]
+    ntiles = n_tiles(s.device_triple()[0] % 16, n_bytes, len(needle))
+    assert tiles_per_workgroup(ntiles, cus, 0) == 1 and ntiles + 2 > 256 and (ntiles + 2) // 256 == 40
     n = len(needle)
     spots = sorted({TILE - 5, 2 * TILE - 1, 64 * MiB - 16, 64 * MiB + 1, n_bytes - n - 1} |
                    {int(x) for x in rng.integers(1, n_bytes - 100, size=300)})

@@ -392,8 +392,8 @@ def test_capacity_cuts_and_the_last_line_at_the_cut(ss):
 
 
 # ---- 7: launch shapes -----------------------------------------------------------------------------------------------------------
-def test_a_large_haystack_two_tiles_per_workgroup(ss):
-    n_bytes = 160 * MiB                                     # (the size and the construction of tests/test_gpu_bounded.py's twin)
+def test_a_160_mib_haystack_of_40_chunks_at_one_tile_per_workgroup(ss):
+    n_bytes = 160 * MiB                                     # (one tile per workgroup; the size and the construction of tests/test_gpu_bounded.py's twin)
     hay = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
     ss.fill_random_device(hay, 0x0B0D)
     hay.masked_fill_(hay == ord("Q"), ord("r"))
@@ -402,6 +402,12 @@ def test_a_large_haystack_two_tiles_per_workgroup(ss):
     rng = np.random.default_rng(88)
     needle = b"quite a long needle, 33 bytes: qz"
     s, s2 = make(ss, needle), make(ss, b"qz")
+    # the shape this size really has (the launch rules as tests/test_gpu_matches.py restates them): 10,240 tiles, ONE per workgroup
+    # - two begin at 2 * CUs * 256 tiles, 2 GiB on 256 CUs - and 10,242 parts, so lines_chunk_kernel has 40 full chunks and the
+    # combine walks them.  Two-tile grids, chunk borders on purpose and runs of chunks: tests/test_gpu_lines_grids.py.
+    cus = ss.device_info()["compute_units"]
+    ntiles = n_tiles(s.device_triple()[0] % 16, n_bytes, len(needle))
+    assert tiles_per_workgroup(ntiles, cus, 0) == 1 and ntiles + 2 > 256 and (ntiles + 2) // 256 == 40
     n = len(needle)
     spots = sorted({TILE - 5, 2 * TILE - 1, 64 * MiB - 16, 64 * MiB + 1, n_bytes - n - 1} |
                    {int(x) for x in rng.integers(1, n_bytes - 100, size=300)})
