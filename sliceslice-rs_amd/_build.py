@@ -1,10 +1,8 @@
 """Builds csrc/ into the in-tree C-ABI libraries with hipcc for gfx950 (cross-compiles without a GPU).
 
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
-    libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES, MORE_LIBRARIES and YET_MORE_LIBRARIES below (service, matches,
-                                  matches_batched, lines, nocase; bounded; inverted), of ONE_MORE_LIBRARY (context), of
-                                  NEXT_LIBRARY (anyof), of SET_LIBRARY (needleset), of OCCURRENCE_LIBRARY (setmatches) and of DISJOINT_LIBRARY
-                                  (disjoint): the
+    libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES below (service, matches, matches_batched, lines, nocase, bounded,
+                                  inverted, context, anyof, needleset, setmatches, disjoint): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -44,65 +42,31 @@ def _library(name, parent, sources, resources=True):
             "resources": os.path.join(_CSRC, "kernel_resources_%s.json" % name) if resources else None}
 
 
-# The opt-in libraries, none of them in the product: name -> its parent (None: the product), the sources it adds to its parent's,
-# its .so and the record of its kernels' registers.  The name is also that of its header (include/sliceslice_hip_<name>.h), of its
-# table and context manager in searcher.py (<NAME>_ABI, <name>_build) and of its lock file (.build_<name>.lock).
+# The opt-in libraries, none of them in the product, each entered ONCE and here: name -> its parent (None: the product; a parent stands
+# before its children), the sources it adds to its parent's, its .so and the record of its kernels' registers.  The name is also that
+# of its header (include/sliceslice_hip_<name>.h), of its table and context manager in searcher.py (<NAME>_ABI, <name>_build), of its
+# lock file (.build_<name>.lock) and of the build_<name> / <name>_library_path / ... functions defined from this table further down.
 LIBRARIES = {
     "service": _library("service", None, ["ss_service.hip"], resources=False),       # (also in the hooks builds)
     "matches": _library("matches", None, ["ss_matches.hip", "scan_inst_all.hip"]),
     "matches_batched": _library("matches_batched", "matches", ["ss_matches_batched.hip", "scan_inst_all_batched.hip"]),
     "lines": _library("lines", "matches", ["ss_lines.hip", "scan_inst_lines.hip"]),
     "nocase": _library("nocase", "lines", ["ss_nocase.hip", "scan_inst_nocase.hip"]),
-}
-# One more, of the same shape and looked up by name like the others (_lib).  It is apart because tests/test_bindings_cpu.py pins
-# list(LIBRARIES) to the five names above; merging the two tables is for a change that may edit that test.
-MORE_LIBRARIES = {
     "bounded": _library("bounded", "nocase", ["ss_bounded.hip", "scan_inst_bounded.hip", "scan_inst_bounded_nocase.hip"]),
-}
-# A third table for the same reason: tests/test_bounded_cpu.py pins list(MORE_LIBRARIES) to ["bounded"].
-YET_MORE_LIBRARIES = {
     "inverted": _library("inverted", "bounded", ["ss_inverted.hip", "scan_inst_inverted.hip", "scan_inst_inverted_nocase.hip"]),
-}
-# A fourth table, again for the same reason: tests/test_inverted_cpu.py pins list(YET_MORE_LIBRARIES) to ["inverted"].
-ONE_MORE_LIBRARY = {
     "context": _library("context", "inverted", ["ss_context.hip"]),
-}
-# A fifth table, again for the same reason: tests/test_context_cpu.py pins list(ONE_MORE_LIBRARY) to ["context"].
-NEXT_LIBRARY = {
     "anyof": _library("anyof", "context", ["ss_anyof.hip"]),
-}
-# A sixth table, again for the same reason: tests/test_anyof_cpu.py pins list(NEXT_LIBRARY) to ["anyof"].
-SET_LIBRARY = {
     "needleset": _library("needleset", "anyof", ["ss_needleset.hip"]),
-}
-# A seventh table, again for the same reason: tests/test_needleset_cpu.py pins list(SET_LIBRARY) to ["needleset"].
-OCCURRENCE_LIBRARY = {
     "setmatches": _library("setmatches", "needleset", ["ss_setmatches.hip"]),
-}
-# An eighth table, again for the same reason: tests/test_setmatches_cpu.py pins list(OCCURRENCE_LIBRARY) to ["setmatches"].
-DISJOINT_LIBRARY = {
     "disjoint": _library("disjoint", "setmatches", ["ss_disjoint.hip"]),
 }
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
-_HEADERS = ["scan_filters.hpp", "scan_kernels.hpp", "scan_launch.hpp", "batched_types.hpp", "batched_kernels.hpp", "service_kernels.hpp", "aux_kernels.hpp",
-            "matches_launch.hpp", "matches_scratch.hpp", "matches_batched_launch.hpp", "lines_tiles.hpp", "lines_kernels.hpp", "lines_launch.hpp", "lines_scan_body.hpp", "lines_host.hpp", "matches_host.hpp",
-            "scan_choice.hpp", "nocase_kernels.hpp", "nocase_launch.hpp", "bounded_kernels.hpp", "bounded_launch.hpp", "bounded_how.hpp",
-            "inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", "anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", "needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", "needleset_host.hpp", "setmatches_kernels.hpp", "setmatches_launch.hpp", "disjoint_kernels.hpp", "disjoint_launch.hpp", "disjoint_host.hpp", "batched_all_kernels.hpp", "prefix_kernel.hpp", "ss_internal.hpp", os.path.join("..", "..", "include", "sliceslice_hip.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_matches.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_matches_batched.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_lines.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_nocase.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_bounded.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_inverted.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_context.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_anyof.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_needleset.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_setmatches.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_disjoint.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_service.h"),
-            os.path.join("..", "..", "include", "sliceslice_hip_tuning.h")]
+# What every object is older than when it is stale: each csrc/*.hpp and each C header include/*.h (the include/*.hpp C++ wrappers are
+# compiled into nothing here), relative to csrc/.  Read from the tree, so that a new header cannot be forgotten.
+_HEADERS = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hpp")) + \
+    sorted(os.path.join("..", "..", "include", f) for f in os.listdir(os.path.join(_ROOT, "include")) if f.endswith(".h"))
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-fvisibility=hidden"]
 _HOOK_FLAGS = ["-DSS_TEST_HOOKS=1"]
 # Host-side sanitizer builds (the reference's guard on its unsafe code is its ASAN CI job,
@@ -267,11 +231,8 @@ def build(force=False, verbose=False):
 
 
 def _lib(name):
-    """The entry of library `name`, from whichever of the eight tables holds it."""
-    for table in (LIBRARIES, MORE_LIBRARIES, YET_MORE_LIBRARIES, ONE_MORE_LIBRARY, NEXT_LIBRARY, SET_LIBRARY, OCCURRENCE_LIBRARY, DISJOINT_LIBRARY):
-        if name in table:
-            return table[name]
-    raise KeyError(name)
+    """The entry of library `name` (KeyError: there is none)."""
+    return LIBRARIES[name]
 
 
 def _all_sources(name):
@@ -280,8 +241,8 @@ def _all_sources(name):
 
 
 def build_library(name, force=False, verbose=False):
-    """The objects of `name`'s parent (built first; they and their resource records are shared) + its own sources ->
-    csrc/libsliceslice_hip_<name>.so.  The kernels of the whole library are recorded in csrc/kernel_resources_<name>.json (the
+    """`name` is a key of LIBRARIES, the one table.  The objects of its parent (built first; they and their resource records are shared)
+    + its own sources -> csrc/libsliceslice_hip_<name>.so.  The kernels of the whole library are recorded in csrc/kernel_resources_<name>.json (the
     service has no kernels of interest and no record)."""
     lib = _lib(name)
     if lib["parent"] is None:
@@ -303,54 +264,20 @@ def library_kernel_resources(name):
     return json.load(open(_lib(name)["resources"]))
 
 
-# The names tests, tools and __graft_entry__ call, one line each over the table.
-def build_service(force=False, verbose=False): return build_library("service", force, verbose)                    # noqa: E704
-def build_matches(force=False, verbose=False): return build_library("matches", force, verbose)                    # noqa: E704
-def build_matches_batched(force=False, verbose=False): return build_library("matches_batched", force, verbose)    # noqa: E704
-def build_lines(force=False, verbose=False): return build_library("lines", force, verbose)                        # noqa: E704
-def build_nocase(force=False, verbose=False): return build_library("nocase", force, verbose)                      # noqa: E704
-def build_bounded(force=False, verbose=False): return build_library("bounded", force, verbose)                    # noqa: E704
-def build_inverted(force=False, verbose=False): return build_library("inverted", force, verbose)                  # noqa: E704
-def build_context(force=False, verbose=False): return build_library("context", force, verbose)                    # noqa: E704
-def build_anyof(force=False, verbose=False): return build_library("anyof", force, verbose)                        # noqa: E704
-def build_needleset(force=False, verbose=False): return build_library("needleset", force, verbose)                # noqa: E704
-def build_setmatches(force=False, verbose=False): return build_library("setmatches", force, verbose)              # noqa: E704
-def build_disjoint(force=False, verbose=False): return build_library("disjoint", force, verbose)                  # noqa: E704
-def service_library_path(): return library_path_of("service")                                                     # noqa: E704
-def matches_library_path(): return library_path_of("matches")                                                     # noqa: E704
-def matches_batched_library_path(): return library_path_of("matches_batched")                                     # noqa: E704
-def lines_library_path(): return library_path_of("lines")                                                         # noqa: E704
-def nocase_library_path(): return library_path_of("nocase")                                                       # noqa: E704
-def bounded_library_path(): return library_path_of("bounded")                                                     # noqa: E704
-def inverted_library_path(): return library_path_of("inverted")                                                   # noqa: E704
-def context_library_path(): return library_path_of("context")                                                     # noqa: E704
-def anyof_library_path(): return library_path_of("anyof")                                                         # noqa: E704
-def needleset_library_path(): return library_path_of("needleset")                                                 # noqa: E704
-def setmatches_library_path(): return library_path_of("setmatches")                                               # noqa: E704
-def disjoint_library_path(): return library_path_of("disjoint")                                                   # noqa: E704
-def matches_resources_path(): return LIBRARIES["matches"]["resources"]                                            # noqa: E704
-def matches_batched_resources_path(): return LIBRARIES["matches_batched"]["resources"]                            # noqa: E704
-def lines_resources_path(): return LIBRARIES["lines"]["resources"]                                                # noqa: E704
-def nocase_resources_path(): return LIBRARIES["nocase"]["resources"]                                              # noqa: E704
-def bounded_resources_path(): return MORE_LIBRARIES["bounded"]["resources"]                                       # noqa: E704
-def inverted_resources_path(): return YET_MORE_LIBRARIES["inverted"]["resources"]                                 # noqa: E704
-def context_resources_path(): return ONE_MORE_LIBRARY["context"]["resources"]                                     # noqa: E704
-def anyof_resources_path(): return NEXT_LIBRARY["anyof"]["resources"]                                             # noqa: E704
-def needleset_resources_path(): return SET_LIBRARY["needleset"]["resources"]                                      # noqa: E704
-def setmatches_resources_path(): return OCCURRENCE_LIBRARY["setmatches"]["resources"]                            # noqa: E704
-def disjoint_resources_path(): return DISJOINT_LIBRARY["disjoint"]["resources"]                                  # noqa: E704
-def matches_kernel_resources(): return library_kernel_resources("matches")                                        # noqa: E704
-def matches_batched_kernel_resources(): return library_kernel_resources("matches_batched")                        # noqa: E704
-def lines_kernel_resources(): return library_kernel_resources("lines")                                            # noqa: E704
-def nocase_kernel_resources(): return library_kernel_resources("nocase")                                          # noqa: E704
-def bounded_kernel_resources(): return library_kernel_resources("bounded")                                        # noqa: E704
+def _wrappers(name):
+    """build_<name>, <name>_library_path and - where the library has a resource record - <name>_resources_path and
+    <name>_kernel_resources: the names tests, tools and documents call, by those names."""
+    def build_it(force=False, verbose=False): return build_library(name, force, verbose)                             # noqa: E704
+    named = {"build_" + name: build_it, name + "_library_path": lambda: library_path_of(name)}
+    if _lib(name)["resources"] is not None:
+        named.update({name + "_resources_path": lambda: _lib(name)["resources"], name + "_kernel_resources": lambda: library_kernel_resources(name)})
+    for public, function in named.items():
+        function.__name__ = function.__qualname__ = public
+    return named
 
-def inverted_kernel_resources(): return library_kernel_resources("inverted")                                      # noqa: E704
-def context_kernel_resources(): return library_kernel_resources("context")                                        # noqa: E704
-def anyof_kernel_resources(): return library_kernel_resources("anyof")                                            # noqa: E704
-def needleset_kernel_resources(): return library_kernel_resources("needleset")                                    # noqa: E704
-def setmatches_kernel_resources(): return library_kernel_resources("setmatches")                                  # noqa: E704
-def disjoint_kernel_resources(): return library_kernel_resources("disjoint")                                      # noqa: E704
+
+for _name in LIBRARIES:
+    globals().update(_wrappers(_name))
 
 
 def build_tools(force=False, verbose=False):

@@ -285,8 +285,7 @@ def _bind(L, table, strict):
 
 
 # What a build of the library may hold beyond the product: feature -> (its table, the symbol `has_<feature>` keys on, what
-# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES, _build.MORE_LIBRARIES and
-# _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY, _build.OCCURRENCE_LIBRARY and _build.DISJOINT_LIBRARY under their names, and the test hooks.
+# _feature_lib says where it is missing).  The opt-in libraries of _build.LIBRARIES under their names, and the test hooks.
 _FEATURES = {
     "hooks": (HOOKS_ABI, "ss_debug_fail_next_scans",
               "this entry point exists in builds with -DSS_TEST_HOOKS only (libsliceslice_hip_tuning.so: "
@@ -376,7 +375,7 @@ def tools_lib():
 
 class _library_build:
     """``with ss.<name>_build():`` - inside the block ``lib()`` is libsliceslice_hip_<name>.so (a key of _build.LIBRARIES,
-    _build.MORE_LIBRARIES, _build.YET_MORE_LIBRARIES, _build.ONE_MORE_LIBRARY, _build.NEXT_LIBRARY, _build.SET_LIBRARY, _build.OCCURRENCE_LIBRARY or _build.DISJOINT_LIBRARY, or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
+    or "tuning"), built and loaded on first use; blocks nest.  Objects remember the library they were made with, so searchers created
     inside keep working (and are freed by the right library) after the block - and a searcher can only use what ITS library holds.
     The subclasses below say what each library adds."""
     name = None

@@ -1,10 +1,9 @@
 """CPU checks of the several-needle calls (include/sliceslice_hip_anyof.h): the header, the ctypes table and the Rust module agree
 symbol by symbol; libsliceslice_hip_anyof.so exports the context library's list plus three functions while every other library
-exports what it did; the fifth build table goes by name like the other four; the two new kernels meet their resource bar and every
+exports what it did; the two new kernels meet their resource bar and every
 row of the context record reappears unchanged; the union rule restated here on numpy arrays reproduces tests/golden/anyof_kat.json
 (GNU grep's output); the index arithmetic of csrc/anyof_segments.hpp passes an exhaustive sweep in a stand-alone host program built
 with ASan and UBSan; the functions are refused outside anyof_build(); tools/grep_hip.py documents and refuses what it should."""
-import ctypes
 import hashlib
 import inspect
 import json
@@ -17,9 +16,9 @@ import numpy as np
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep
-from test_context_cpu import CONTEXT, checksum, context_prototypes, context_rule, selected_numbers, separators
+from test_context_cpu import CONTEXT, checksum, context_rule, selected_numbers, separators
 from test_inverted_cpu import INVERTED, all_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,51 +45,22 @@ def test_the_rule_on_small_cases():
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def anyof_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_anyof.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+int\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(2).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(1)] = ("i32", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_anyof.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "u32": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*->\s*([^;]+);", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()], ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = anyof_prototypes()
+    c = header_prototypes("sliceslice_hip_anyof.h")
     assert sorted(c) == sorted(ss.searcher.ANYOF_ABI) == sorted(ANYOF)
     # the find call is the context call with (searchers, needles) in the searcher's place; the count call is its head and `lines`
-    context = context_prototypes()["ss_find_lines_context_device"][1]
+    context = header_prototypes("sliceslice_hip_context.h")["ss_find_lines_context_device"][1]
     assert c["ss_find_lines_anyof_device"][1] == ["ptr", "u32"] + context[1:]
     assert c["ss_count_lines_anyof_device"][1] == ["ptr", "u32"] + context[1:5] + ["ptr", "ptr"]
     assert c["ss_union_numbers_device"][1] == ["ptr", "ptr", "ptr", "u32", "u64", "i32", "ptr", "ptr", "u64", "ptr"]
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_anyof.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_anyof.rs")).read()
     assert r == c, (r, c)
-
-    def cls(t):
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_uint32: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.ANYOF_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
-    assert not set(c) & (set(context_prototypes()) | set(BOUNDED) | set(INVERTED))
+    assert not set(c) & (set(header_prototypes("sliceslice_hip_context.h")) | set(BOUNDED) | set(INVERTED))
     text = open(os.path.join(ROOT, "include", "sliceslice_hip_anyof.h")).read()
     assert '#include "sliceslice_hip_context.h"' in text and "#define SS_BOUND" not in text and "#define SS_CONTEXT" not in text
     most = int(re.search(r"#define SS_ANYOF_MAX_NEEDLES\s+(\d+)u\b", text).group(1))
@@ -127,41 +97,6 @@ def test_the_anyof_library_exports_the_context_list_plus_three_and_the_others_wh
     assert _exported(b.build_lines()) == sorted(product + matches + LINES)
     assert _exported(b.build_nocase()) == sorted(product + matches + LINES + NOCASE)
     assert os.path.basename(b.anyof_library_path()) == "libsliceslice_hip_anyof.so"
-
-
-def test_the_fifth_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.NEXT_LIBRARY) == ["anyof"]
-    assert not set(b.NEXT_LIBRARY) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES) | set(b.YET_MORE_LIBRARIES) | set(b.ONE_MORE_LIBRARY))
-    entry = b.NEXT_LIBRARY["anyof"]
-    assert entry["parent"] == "context" and entry["sources"] == ["ss_anyof.hip"] and b._lib("anyof") is entry
-    assert os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", "ss_anyof.hip"))
-    for name in ("service", "matches", "matches_batched", "lines", "nocase", "bounded", "inverted", "context"):
-        assert b._lib(name)["so"].endswith("libsliceslice_hip_%s.so" % name)
-    with pytest.raises(KeyError):
-        b._lib("no such library")
-    assert b.library_path_of("anyof") == entry["so"] == b.anyof_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_anyof.json" == os.path.basename(b.anyof_resources_path())
-    assert b._all_sources("anyof") == b._all_sources("context") + ["ss_anyof.hip"]
-    for h in ("anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp", os.path.join("..", "..", "include", "sliceslice_hip_anyof.h")):
-        assert h in b._HEADERS, h                                # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["anyof"][0] is ss.searcher.ANYOF_ABI and ss.searcher._FEATURES["anyof"][1] == "ss_union_numbers_device"
-    product = ss.lib()
-    assert not product.has_anyof
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.anyof_build\(\)") as e:
-        ss.searcher._feature_lib(product, "anyof")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.anyof_build() as L:
-        assert ss.lib() is L and L.has_anyof and L.has_context and L.has_inverted and L.has_bounded and L.has_nocase and L.has_lines and L.has_matches
-        assert not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.context_build() as L:
-        assert not L.has_anyof
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("b.build_context(") < entry_point.index("b.build_anyof(force=True, verbose=True)") < entry_point.index("b.build_tuning(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_anyof.json" in ignored
-    assert "fifth table" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.13", 1)[1]            # why there are five tables
 
 
 def test_the_union_kernels_meet_their_bar_and_every_other_row_is_what_it_was():

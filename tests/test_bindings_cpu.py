@@ -29,7 +29,8 @@ def _c_class(t):
     if "*" in t or "[" in t:
         return "ptr"
     t = re.sub(r"\bconst\b", "", t).strip()
-    return {"int": "i32", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "float": "f32", "double": "f64", "void": "void"}[t]
+    return {"int": "i32", "unsigned": "u32", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "float": "f32", "double": "f64",
+            "void": "void"}[t]
 
 
 def header_prototypes(header="sliceslice_hip.h"):
@@ -58,7 +59,7 @@ def _rust_class(t):
     t = t.strip()
     if t.startswith("*"):
         return "ptr"
-    return {"c_int": "i32", "usize": "usize", "u64": "u64", "u32": "u32", "c_float": "f32", "f64": "f64"}[t]
+    return {"c_int": "i32", "c_uint": "u32", "usize": "usize", "u64": "u64", "u32": "u32", "c_float": "f32", "f64": "f64"}[t]
 
 
 def rust_prototypes(source="hip.rs"):
@@ -84,10 +85,14 @@ def exported(path):
 
 
 def ctypes_class(t):
-    """pointer / integer width class of an entry of a ctypes table, as header_prototypes spells it"""
-    if t in (ctypes.c_void_p,) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+    """pointer / integer width class of an entry of a ctypes table, as header_prototypes spells it.  c_size_t and c_uint64 are one
+    ctypes type on this ABI (and c_uint32 is c_uint), so both come out as "u64": callers compare after usize -> u64."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
         return "ptr"
-    return {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64"}[t]
+    return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64", ctypes.c_float: "f32",
+            ctypes.c_double: "f64"}[t]
 
 
 def test_header_parser_sees_every_symbol():
@@ -130,15 +135,7 @@ def test_rust_extern_block_matches_the_header():
 
 
 def test_ctypes_table_matches_the_header():
-    c = header_prototypes()
-
-    def cls(t):
-        if t is None:
-            return "void"
-        if t in (ctypes.c_void_p, ctypes.c_char_p) or hasattr(t, "contents") or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_size_t: "usize", ctypes.c_uint64: "u64", ctypes.c_uint32: "u32", ctypes.c_float: "f32",
-                ctypes.c_double: "f64"}[t]
+    c, cls = header_prototypes(), ctypes_class
     c.update(header_prototypes("sliceslice_hip_tuning.h"))
     c.update(header_prototypes("sliceslice_hip_service.h"))
     tables = dict(ss.searcher.ABI, **ss.searcher.TOOLS_ABI, **ss.searcher.HOOKS_ABI, **ss.searcher.SERVICE_ABI)
@@ -150,20 +147,60 @@ def test_ctypes_table_matches_the_header():
         assert norm(got) == norm(want), (name, got, want)
 
 
+# What the one table holds: name -> (parent, the sources it adds, the internal headers it is known to need, the symbol has_<name>
+# keys on where that is pinned).  Every library's own header, include/sliceslice_hip_<name>.h, is expected besides.
+EXPECTED_LIBRARIES = {
+    "service": (None, ["ss_service.hip"], [], None),
+    "matches": (None, ["ss_matches.hip", "scan_inst_all.hip"], [], None),
+    "matches_batched": ("matches", ["ss_matches_batched.hip", "scan_inst_all_batched.hip"], [], None),
+    "lines": ("matches", ["ss_lines.hip", "scan_inst_lines.hip"], [], None),
+    "nocase": ("lines", ["ss_nocase.hip", "scan_inst_nocase.hip"], [], None),
+    "bounded": ("nocase", ["ss_bounded.hip", "scan_inst_bounded.hip", "scan_inst_bounded_nocase.hip"], [], None),
+    "inverted": ("bounded", ["ss_inverted.hip", "scan_inst_inverted.hip", "scan_inst_inverted_nocase.hip"],
+                 ["inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "bounded_how.hpp"], None),
+    "context": ("inverted", ["ss_context.hip"], ["context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp"], None),
+    "anyof": ("context", ["ss_anyof.hip"], ["anyof_kernels.hpp", "anyof_launch.hpp", "anyof_segments.hpp"], "ss_union_numbers_device"),
+    "needleset": ("anyof", ["ss_needleset.hip"], ["needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp"], "ss_needle_set_new"),
+    "setmatches": ("needleset", ["ss_setmatches.hip"],
+                   ["setmatches_kernels.hpp", "setmatches_launch.hpp", "needleset_host.hpp", "needleset_tables.hpp"], "ss_count_set_device"),
+    "disjoint": ("setmatches", ["ss_disjoint.hip"], ["disjoint_kernels.hpp", "disjoint_launch.hpp", "disjoint_host.hpp"], "ss_count_disjoint_device"),
+}
+DELETED_TABLES = ["MORE_LIBRARIES", "YET_MORE_LIBRARIES", "ONE_MORE_LIBRARY", "NEXT_LIBRARY", "SET_LIBRARY", "OCCURRENCE_LIBRARY", "DISJOINT_LIBRARY"]
+
+
 def test_every_library_of_the_table_has_its_header_table_context_flag_and_guard():
     """_build.LIBRARIES is the one place a library is entered: everything else about it goes by its name."""
-    libraries = build_module().LIBRARIES
-    assert list(libraries) == ["service", "matches", "matches_batched", "lines", "nocase"]
+    b = build_module()
+    libraries, csrc = b.LIBRARIES, os.path.join(ROOT, "sliceslice-rs_amd", "csrc")
+    assert list(libraries) == list(EXPECTED_LIBRARIES)
+    with pytest.raises(KeyError):
+        b._lib("no such library")
+    # a change to any internal header or C header rebuilds the objects: the list is the tree's
+    on_disk = [f for f in os.listdir(csrc) if f.endswith(".hpp")] + \
+        [os.path.join("..", "..", "include", f) for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")]
+    assert sorted(b._HEADERS) == sorted(on_disk) and len(on_disk) >= 57
+    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
     product = ss.lib()
     for name, entry in libraries.items():
-        assert entry["parent"] is None or entry["parent"] in libraries, name
+        parent, sources, headers, symbol = EXPECTED_LIBRARIES[name]
+        assert entry["parent"] is None or entry["parent"] in list(libraries)[:list(libraries).index(name)], name
+        assert entry["parent"] == parent and entry["sources"] == sources and b._lib(name) is entry, name
+        assert all(os.path.exists(os.path.join(csrc, s)) for s in entry["sources"]), name
+        assert b.library_path_of(name) == entry["so"] == getattr(b, name + "_library_path")(), name
         assert os.path.basename(entry["so"]) == "libsliceslice_hip_%s.so" % name
-        assert all(os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", s)) for s in entry["sources"]), name
+        if name == "service":
+            assert entry["resources"] is None and not hasattr(b, "service_resources_path") and not hasattr(b, "service_kernel_resources")
+        else:
+            assert os.path.basename(entry["resources"]) == "kernel_resources_%s.json" % name == os.path.basename(getattr(b, name + "_resources_path")())
+            assert "sliceslice-rs_amd/csrc/" + os.path.basename(entry["resources"]) in ignored, name
+        assert b._all_sources(name) == b._all_sources(parent) + sources, name
         header = "sliceslice_hip_%s.h" % name
-        assert os.path.exists(os.path.join(ROOT, "include", header)), header
+        for h in headers + [os.path.join("..", "..", "include", header)]:
+            assert h in b._HEADERS and os.path.exists(os.path.join(csrc, h)), h
         table = getattr(ss.searcher, name.upper() + "_ABI")
         assert sorted(table) == sorted(header_prototypes(header)), name
         assert ss.searcher._FEATURES[name][0] is table and ss.searcher._FEATURES[name][1] in table, name
+        assert symbol is None or ss.searcher._FEATURES[name][1] == symbol, name
         context = getattr(ss, name + "_build")
         assert not getattr(product, "has_" + name), name
         with pytest.raises(ss.SlicesliceError, match=r"ss\.%s_build\(\)" % name) as e:
@@ -180,6 +217,26 @@ def test_every_library_of_the_table_has_its_header_table_context_flag_and_guard(
                 assert ss.lib() is inner
             assert ss.lib() is L
         assert ss.lib() is product
+
+
+def test_the_one_table_is_what_the_entry_point_builds_and_the_documents_describe():
+    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    # the whole table (the colon: no slice of it), in its pinned order, before the tuning build - and no library by hand
+    assert entry_point.index("for name in b.LIBRARIES:") < entry_point.index("b.build_library(name, force=True, verbose=True)") < entry_point.index("b.build_tuning(")
+    assert not [name for name in EXPECTED_LIBRARIES if "b.build_%s(" % name in entry_point]
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    paragraph = [p for p in design.split("\n\n") if "opt-in libraries" in p and "entered ONCE" in p]
+    assert len(paragraph) == 1 and "`LIBRARIES`" in paragraph[0]
+    assert all(re.search(r"\b%s\b" % name, paragraph[0]) for name in EXPECTED_LIBRARIES)
+    # the seven tables that stood next to it are gone from the code and from the two documents (this file names them to say so)
+    texts = [os.path.join(ROOT, "README.md"), os.path.join(ROOT, "DESIGN.md")]
+    for folder, dirs, files in os.walk(ROOT):
+        dirs[:] = [d for d in dirs if not d.startswith(".")]
+        texts += [os.path.join(folder, f) for f in files if f.endswith(".py")]
+    for path in texts:
+        if os.path.abspath(path) != os.path.abspath(__file__):
+            text = open(path, errors="replace").read()
+            assert not [t for t in DELETED_TABLES if t in text], path
 
 
 def _bench(args, env_extra=None):

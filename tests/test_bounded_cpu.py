@@ -1,10 +1,9 @@
 """CPU checks of the whole-word / whole-line calls (include/sliceslice_hip_bounded.h): the header, the ctypes table and the Rust
 module agree symbol by symbol and are the models' argument lists with `unsigned how` inserted; libsliceslice_hip_bounded.so exports
-exactly the five headers while the product and the five libraries of the first table export what they did; the 36 bounded kernels
+exactly the five headers while the product and the five earlier libraries export what they did; the 36 bounded kernels
 meet the scan kernels' bar, sit in their two translation units and in no other library's record, and the nocase library's record
 reappears unchanged; the rule restated here reproduces tests/golden/bounded_kat.json; the keywords are refused outside
 bounded_build(); tools/grep_hip.py refuses what the library refuses."""
-import ctypes
 import inspect
 import json
 import os
@@ -15,7 +14,7 @@ import sys
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -73,33 +72,8 @@ def bounded_lines_rule(data, needle, delimiter, line, nocase=False):
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def bounded_prototypes():
-    """header_prototypes for this header, whose `unsigned how` the shared parser has no class for: "u32" here"""
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_bounded.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+int\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(2).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(1)] = ("i32", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_bounded.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*->\s*([^;]+);", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()], ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = bounded_prototypes()
+    c = header_prototypes("sliceslice_hip_bounded.h")
     assert sorted(c) == sorted(ss.searcher.BOUNDED_ABI) == sorted(BOUNDED)
     # the argument lists of the models with `how` in front of the stream
     m, l = header_prototypes("sliceslice_hip_matches.h"), header_prototypes("sliceslice_hip_lines.h")
@@ -107,15 +81,10 @@ def test_header_ctypes_and_rust_agree():
                               ("ss_count_lines_device", l, 4), ("ss_count_lines_device_async", l, 4), ("ss_find_lines_device", l, 4)):
         res, args = protos[model]
         assert c[model.replace("_device", "_bounded_device")] == (res, args[:at] + ["u32"] + args[at:]), model
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_bounded.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_bounded.rs")).read()
     assert r == c, (r, c)
-
-    def cls(t):
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.BOUNDED_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
@@ -143,31 +112,6 @@ def test_the_bounded_library_exports_five_headers_and_the_others_what_they_did()
     assert _exported(b.build_lines()) == sorted(product + matches + LINES)
     assert _exported(b.build_nocase()) == sorted(product + matches + LINES + NOCASE)
     assert os.path.basename(b.bounded_library_path()) == "libsliceslice_hip_bounded.so"
-
-
-def test_the_second_table_goes_by_name_like_the_first():
-    b = _build()
-    assert list(b.MORE_LIBRARIES) == ["bounded"] and not set(b.MORE_LIBRARIES) & set(b.LIBRARIES)
-    entry = b.MORE_LIBRARIES["bounded"]
-    assert entry["parent"] == "nocase" and entry["sources"] == ["ss_bounded.hip", "scan_inst_bounded.hip", "scan_inst_bounded_nocase.hip"]
-    assert all(os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", s)) for s in entry["sources"])
-    assert b.library_path_of("bounded") == entry["so"] == b.bounded_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_bounded.json" == os.path.basename(b.bounded_resources_path())
-    assert b._all_sources("bounded") == b._all_sources("nocase") + entry["sources"]
-    assert ss.searcher._FEATURES["bounded"][0] is ss.searcher.BOUNDED_ABI and ss.searcher._FEATURES["bounded"][1] in BOUNDED
-    product = ss.lib()
-    assert not product.has_bounded
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.bounded_build\(\)") as e:
-        ss.searcher._feature_lib(product, "bounded")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.bounded_build() as L:
-        assert ss.lib() is L and L.has_bounded and L.has_nocase and L.has_lines and L.has_matches
-        assert not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.nocase_build() as L:
-        assert not L.has_bounded
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("for name in b.LIBRARIES") < entry_point.index("b.build_bounded(")
 
 
 def test_the_bounded_kernels_meet_the_scan_kernels_bar():

@@ -1,10 +1,9 @@
 """CPU checks of the context calls (include/sliceslice_hip_context.h): the header, the ctypes table and the Rust module agree symbol
 by symbol; libsliceslice_hip_context.so exports the six earlier headers plus two functions while every other library exports what
-it did; the fourth build table goes by name like the other three; the new kernels meet their resource bar and every row of the
+it did; the new kernels meet their resource bar and every row of the
 other records is what it was; tools/grep_hip.py documents and refuses what the issue lists; the rule restated here on numpy arrays
 reproduces tests/golden/context_kat.json (GNU grep's output); the range arithmetic of csrc/context_ranges.hpp passes an exhaustive
 sweep in a stand-alone host program built with ASan and UBSan; the methods are refused outside context_build()."""
-import ctypes
 import hashlib
 import inspect
 import json
@@ -17,7 +16,7 @@ import numpy as np
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep
 from test_inverted_cpu import INVERTED, all_lines, inverted_lines_rule
 
@@ -71,46 +70,17 @@ def test_the_rule_on_small_cases():
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def context_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_context.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+int\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(2).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(1)] = ("i32", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_context.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*->\s*([^;]+);", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()], ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = context_prototypes()
+    c = header_prototypes("sliceslice_hip_context.h")
     assert sorted(c) == sorted(ss.searcher.CONTEXT_ABI) == sorted(CONTEXT)
     # (searcher, haystack, len, delimiter, ...) as in the line calls; the outputs are the line calls' three arrays plus the kinds
     find_lines = header_prototypes("sliceslice_hip_lines.h")["ss_find_lines_device"][1]
     assert c["ss_lines_around_device"][1] == find_lines[:4] + ["ptr", "u64", "u64", "u64"] + find_lines[4:8] + ["ptr"] + find_lines[8:]
     assert c["ss_find_lines_context_device"][1] == find_lines[:4] + ["u32", "u64", "u64"] + find_lines[4:8] + ["ptr"] + find_lines[8:] + ["ptr"]
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_context.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_context.rs")).read()
     assert r == c, (r, c)
-
-    def cls(t):
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.CONTEXT_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
@@ -148,41 +118,6 @@ def test_the_context_library_exports_six_headers_plus_two_and_the_others_what_th
     assert _exported(b.build_lines()) == sorted(product + matches + LINES)
     assert _exported(b.build_nocase()) == sorted(product + matches + LINES + NOCASE)
     assert os.path.basename(b.context_library_path()) == "libsliceslice_hip_context.so"
-
-
-def test_the_fourth_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.ONE_MORE_LIBRARY) == ["context"]
-    assert not set(b.ONE_MORE_LIBRARY) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES) | set(b.YET_MORE_LIBRARIES))
-    entry = b.ONE_MORE_LIBRARY["context"]
-    assert entry["parent"] == "inverted" and entry["sources"] == ["ss_context.hip"] and b._lib("context") is entry
-    assert os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", "ss_context.hip"))
-    for name in ("service", "matches", "matches_batched", "lines", "nocase", "bounded", "inverted"):
-        assert b._lib(name)["so"].endswith("libsliceslice_hip_%s.so" % name)
-    with pytest.raises(KeyError):
-        b._lib("no such library")
-    assert b.library_path_of("context") == entry["so"] == b.context_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_context.json" == os.path.basename(b.context_resources_path())
-    assert b._all_sources("context") == b._all_sources("inverted") + ["ss_context.hip"]
-    for h in ("context_kernels.hpp", "context_launch.hpp", "context_ranges.hpp", os.path.join("..", "..", "include", "sliceslice_hip_context.h")):
-        assert h in b._HEADERS, h                                # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["context"][0] is ss.searcher.CONTEXT_ABI and ss.searcher._FEATURES["context"][1] in CONTEXT
-    product = ss.lib()
-    assert not product.has_context
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.context_build\(\)") as e:
-        ss.searcher._feature_lib(product, "context")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.context_build() as L:
-        assert ss.lib() is L and L.has_context and L.has_inverted and L.has_bounded and L.has_nocase and L.has_lines and L.has_matches
-        assert not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.inverted_build() as L:
-        assert not L.has_context
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("b.build_inverted(") < entry_point.index("b.build_context(") < entry_point.index("b.build_tuning(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_context.json" in ignored
-    assert "fourth table" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.12", 1)[1]          # why there are four tables
 
 
 def test_the_context_kernels_meet_their_bar_and_every_other_row_is_what_it_was():

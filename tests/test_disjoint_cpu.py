@@ -1,11 +1,10 @@
 """CPU checks of the non-overlapping calls (include/sliceslice_hip_disjoint.h): the header, the ctypes table and the Rust module agree
 symbol by symbol; libsliceslice_hip_disjoint.so exports the setmatches library's list plus four functions while every other library
-exports what it did; the eighth build table goes by name like the other seven; the new kernels use no private segment and every row
+exports what it did; the new kernels use no private segment and every row
 of the setmatches record reappears unchanged; the border function and the greedy walk of csrc/disjoint_host.hpp pass a sweep
 against brute force in a stand-alone host program built with ASan and UBSan; tests/golden/disjoint_kat.json is what bytes.count and
 re.finditer give; the new Python methods are refused outside disjoint_build(); tools/grep_hip.py documents -o and --replace and
 refuses what it should."""
-import ctypes
 import hashlib
 import inspect
 import json
@@ -19,12 +18,12 @@ import pytest
 
 import sliceslice_rs_amd as ss
 from test_anyof_cpu import ANYOF
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep
 from test_context_cpu import CONTEXT
 from test_inverted_cpu import INVERTED
-from test_needleset_cpu import NEEDLESET, needleset_prototypes
-from test_setmatches_cpu import SETMATCHES, setmatches_prototypes
+from test_needleset_cpu import NEEDLESET
+from test_setmatches_cpu import SETMATCHES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -34,54 +33,23 @@ KERNELS = ["ss::disjoint_block_kernel", "ss::disjoint_chain_kernel", "ss::disjoi
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def disjoint_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_disjoint.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+(int|void)\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(3).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(2)] = ("i32" if m.group(1) == "int" else "void", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_disjoint.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "u32": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*(?:->\s*([^;]+))?;", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()] if m.group(3) else "void", ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = disjoint_prototypes()
+    c = header_prototypes("sliceslice_hip_disjoint.h")
     assert sorted(c) == sorted(ss.searcher.DISJOINT_ABI) == sorted(DISJOINT)
     assert c["ss_select_disjoint_device"] == ("i32", ["ptr", "ptr", "u64", "u64", "ptr", "ptr", "u64", "ptr"])
     # the models' argument lists: (searcher, haystack, len, how, stream, ...)
     assert c["ss_count_disjoint_device"] == ("i32", ["ptr", "ptr", "usize", "u32", "ptr", "ptr"])
     assert c["ss_find_all_disjoint_device"] == ("i32", ["ptr", "ptr", "usize", "u32", "ptr", "ptr", "u64", "ptr"])
     assert c["ss_replace_device"] == ("i32", ["ptr", "ptr", "usize", "u32", "ptr", "usize", "ptr", "ptr", "u64", "ptr", "ptr"])
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_disjoint.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_disjoint.rs")).read()
     assert r == c, (r, c)
     assert "pub const SS_DISJOINT_BLOCK: u64 = 4096;" in rust
-
-    def cls(t):
-        if t is None:
-            return "void"
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_uint32: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.DISJOINT_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
-    assert not set(c) & (set(setmatches_prototypes()) | set(needleset_prototypes()) | set(BOUNDED) | set(INVERTED) | set(CONTEXT) | set(ANYOF))
+    assert not set(c) & (set(header_prototypes("sliceslice_hip_setmatches.h")) | set(header_prototypes("sliceslice_hip_needleset.h")) | set(BOUNDED) | set(INVERTED) | set(CONTEXT) | set(ANYOF))
     text = open(os.path.join(ROOT, "include", "sliceslice_hip_disjoint.h")).read()
     assert '#include "sliceslice_hip_setmatches.h"' in text and "#define SS_BOUND" not in text and "typedef struct" not in text
     assert re.search(r"#define SS_DISJOINT_BLOCK\s+4096u", text) and ss.DISJOINT_BLOCK == ss.searcher.DISJOINT_BLOCK == 4096
@@ -128,43 +96,6 @@ def test_the_disjoint_library_exports_the_setmatches_list_plus_four_and_the_othe
     assert _exported(ss.build()) == sorted(product)
     assert _exported(b.build_matches()) == sorted(product + matches)
     assert os.path.basename(b.disjoint_library_path()) == "libsliceslice_hip_disjoint.so"
-
-
-def test_the_eighth_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.DISJOINT_LIBRARY) == ["disjoint"] and list(b.OCCURRENCE_LIBRARY) == ["setmatches"]
-    assert not set(b.DISJOINT_LIBRARY) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES) | set(b.YET_MORE_LIBRARIES) | set(b.ONE_MORE_LIBRARY) |
-                                          set(b.NEXT_LIBRARY) | set(b.SET_LIBRARY) | set(b.OCCURRENCE_LIBRARY))
-    entry = b.DISJOINT_LIBRARY["disjoint"]
-    assert entry["parent"] == "setmatches" and entry["sources"] == ["ss_disjoint.hip"] and b._lib("disjoint") is entry
-    assert os.path.exists(os.path.join(CSRC, "ss_disjoint.hip"))
-    for name in ("service", "matches", "matches_batched", "lines", "nocase", "bounded", "inverted", "context", "anyof", "needleset", "setmatches",
-                 "disjoint"):
-        assert b._lib(name)["so"].endswith("libsliceslice_hip_%s.so" % name)
-    with pytest.raises(KeyError):
-        b._lib("no such library")
-    assert b.library_path_of("disjoint") == entry["so"] == b.disjoint_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_disjoint.json" == os.path.basename(b.disjoint_resources_path())
-    assert b._all_sources("disjoint") == b._all_sources("setmatches") + ["ss_disjoint.hip"]
-    for h in ("disjoint_kernels.hpp", "disjoint_launch.hpp", "disjoint_host.hpp", os.path.join("..", "..", "include", "sliceslice_hip_disjoint.h")):
-        assert h in b._HEADERS and os.path.exists(os.path.join(CSRC, h)), h        # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["disjoint"][0] is ss.searcher.DISJOINT_ABI and ss.searcher._FEATURES["disjoint"][1] == "ss_count_disjoint_device"
-    product = ss.lib()
-    assert not product.has_disjoint
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.disjoint_build\(\)") as e:
-        ss.searcher._feature_lib(product, "disjoint")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.disjoint_build() as L:
-        assert ss.lib() is L and L.has_disjoint and L.has_setmatches and L.has_needleset and L.has_anyof and L.has_context and L.has_inverted
-        assert L.has_bounded and L.has_nocase and L.has_lines and L.has_matches and not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.setmatches_build() as L:
-        assert not L.has_disjoint
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("b.build_setmatches(") < entry_point.index("b.build_disjoint(force=True, verbose=True)") < entry_point.index("b.build_tuning(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_disjoint.json" in ignored
-    assert "eighth table" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.16", 1)[1]          # why there are eight tables
 
 
 def test_the_new_kernels_use_no_private_segment_and_every_other_row_is_what_it_was():

@@ -1,11 +1,9 @@
 """CPU checks of the inverted line calls (include/sliceslice_hip_inverted.h): the header, the ctypes table and the Rust module
 agree symbol by symbol and are the line calls' argument lists with `unsigned how` behind the delimiter;
-libsliceslice_hip_inverted.so exports exactly the six headers while every other library exports what it did; the third build table
-goes by name like the other two; the 36 inverted emit kernels meet the scan kernels' bar, sit in their two translation units and
+libsliceslice_hip_inverted.so exports exactly the six headers while every other library exports what it did; the 36 inverted emit kernels meet the scan kernels' bar, sit in their two translation units and
 in no other library's record, and the bounded library's record reappears unchanged; the rule restated here reproduces
 tests/golden/inverted_kat.json; the methods are refused outside inverted_build(); tools/grep_hip.py refuses what has no
 complement."""
-import ctypes
 import inspect
 import json
 import os
@@ -14,8 +12,8 @@ import re
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
-from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep, bounded_lines_rule, bounded_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
+from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep, bounded_lines_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -50,47 +48,18 @@ def inverted_lines_rule(data, needle, delimiter, how):
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def inverted_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_inverted.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+int\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(2).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(1)] = ("i32", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_inverted.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*->\s*([^;]+);", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()], ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = inverted_prototypes()
+    c = header_prototypes("sliceslice_hip_inverted.h")
     assert sorted(c) == sorted(ss.searcher.INVERTED_ABI) == sorted(INVERTED)
     # the argument lists of the models with `how` behind the delimiter - exactly the bounded line calls'
-    l, b = header_prototypes("sliceslice_hip_lines.h"), bounded_prototypes()
+    l, b = header_prototypes("sliceslice_hip_lines.h"), header_prototypes("sliceslice_hip_bounded.h")
     for model in LINES:
         res, args = l[model]
         assert c[model.replace("_device", "_inverted_device")] == (res, args[:4] + ["u32"] + args[4:]) == b[model.replace("_device", "_bounded_device")], model
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_inverted.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_inverted.rs")).read()
     assert r == c, (r, c)
-
-    def cls(t):
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.INVERTED_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
@@ -123,38 +92,6 @@ def test_the_inverted_library_exports_six_headers_and_the_others_what_they_did()
     assert _exported(b.build_lines()) == sorted(product + matches + LINES)
     assert _exported(b.build_nocase()) == sorted(product + matches + LINES + NOCASE)
     assert os.path.basename(b.inverted_library_path()) == "libsliceslice_hip_inverted.so"
-
-
-def test_the_third_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.YET_MORE_LIBRARIES) == ["inverted"]
-    assert not set(b.YET_MORE_LIBRARIES) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES))
-    entry = b.YET_MORE_LIBRARIES["inverted"]
-    own = ["ss_inverted.hip", "scan_inst_inverted.hip", "scan_inst_inverted_nocase.hip"]
-    assert entry["parent"] == "bounded" and entry["sources"] == own and b._lib("inverted") is entry
-    assert all(os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", s)) for s in own)
-    assert b.library_path_of("inverted") == entry["so"] == b.inverted_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_inverted.json" == os.path.basename(b.inverted_resources_path())
-    assert b._all_sources("inverted") == b._all_sources("bounded") + own
-    for h in ("inverted_kernels.hpp", "inverted_small_kernels.hpp", "inverted_launch.hpp", "bounded_how.hpp"):
-        assert h in b._HEADERS, h                                # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["inverted"][0] is ss.searcher.INVERTED_ABI and ss.searcher._FEATURES["inverted"][1] in INVERTED
-    product = ss.lib()
-    assert not product.has_inverted
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.inverted_build\(\)") as e:
-        ss.searcher._feature_lib(product, "inverted")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.inverted_build() as L:
-        assert ss.lib() is L and L.has_inverted and L.has_bounded and L.has_nocase and L.has_lines and L.has_matches
-        assert not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.bounded_build() as L:
-        assert not L.has_inverted
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("for name in b.LIBRARIES") < entry_point.index("b.build_bounded(") < entry_point.index("b.build_inverted(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_inverted.json" in ignored
-    assert "merging" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.11", 1)[1]        # why there are three tables
 
 
 def test_the_inverted_kernels_meet_the_scan_kernels_bar():

@@ -1,10 +1,9 @@
 """CPU checks of the needle-set calls (include/sliceslice_hip_needleset.h): the header, the ctypes table and the Rust module agree
 symbol by symbol; libsliceslice_hip_needleset.so exports the anyof library's list plus five functions while every other library
-exports what it did; the sixth build table goes by name like the other five; the six set kernels meet their resource bar and every
+exports what it did; the six set kernels meet their resource bar and every
 row of the anyof record reappears unchanged; the tables and the lookup of csrc/needleset_tables.hpp pass a sweep against a
 brute-force memcmp loop in a stand-alone host program built with ASan and UBSan; the set is refused outside needleset_build();
 tools/grep_hip.py documents --one-pass and refuses what it should."""
-import ctypes
 import inspect
 import json
 import os
@@ -15,10 +14,10 @@ import subprocess
 import pytest
 
 import sliceslice_rs_amd as ss
-from test_anyof_cpu import ANYOF, anyof_prototypes
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_anyof_cpu import ANYOF
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep
-from test_context_cpu import CONTEXT, context_prototypes
+from test_context_cpu import CONTEXT
 from test_inverted_cpu import INVERTED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,54 +26,23 @@ NEEDLESET = ["ss_needle_set_new", "ss_needle_set_free", "ss_needle_set_info", "s
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def needleset_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_needleset.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+(int|void)\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(3).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(2)] = ("i32" if m.group(1) == "int" else "void", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_needleset.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "u32": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*(?:->\s*([^;]+))?;", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()] if m.group(3) else "void", ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = needleset_prototypes()
+    c = header_prototypes("sliceslice_hip_needleset.h")
     assert sorted(c) == sorted(ss.searcher.NEEDLESET_ABI) == sorted(NEEDLESET)
     # the line calls are the anyof calls with the set in the place of (searchers, needles)
-    anyof = anyof_prototypes()
+    anyof = header_prototypes("sliceslice_hip_anyof.h")
     assert c["ss_find_lines_set_device"][1] == ["ptr"] + anyof["ss_find_lines_anyof_device"][1][2:]
     assert c["ss_count_lines_set_device"][1] == ["ptr"] + anyof["ss_count_lines_anyof_device"][1][2:]
     assert c["ss_needle_set_new"] == ("i32", ["ptr", "ptr", "u32", "u32", "ptr"]) and c["ss_needle_set_free"] == ("void", ["ptr"])
     assert c["ss_needle_set_info"] == ("i32", ["ptr", "ptr"])
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_needleset.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_needleset.rs")).read()
     assert r == c, (r, c)
-
-    def cls(t):
-        if t is None:
-            return "void"
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_uint32: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.NEEDLESET_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
-    assert not set(c) & (set(context_prototypes()) | set(BOUNDED) | set(INVERTED) | set(anyof))
+    assert not set(c) & (set(header_prototypes("sliceslice_hip_context.h")) | set(BOUNDED) | set(INVERTED) | set(anyof))
     text = open(os.path.join(ROOT, "include", "sliceslice_hip_needleset.h")).read()
     assert '#include "sliceslice_hip_anyof.h"' in text and "#define SS_BOUND" not in text and "#define SS_CONTEXT" not in text
     assert "#define SS_ANYOF" not in text and int(re.search(r"#define SS_SET_NOCASE\s+(\d+)u\b", text).group(1)) == ss.SS_SET_NOCASE == 1
@@ -110,41 +78,6 @@ def test_the_needleset_library_exports_the_anyof_list_plus_five_and_the_others_w
     assert _exported(ss.build()) == sorted(product)
     assert _exported(b.build_lines()) == sorted(product + matches + LINES)
     assert os.path.basename(b.needleset_library_path()) == "libsliceslice_hip_needleset.so"
-
-
-def test_the_sixth_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.SET_LIBRARY) == ["needleset"] and list(b.NEXT_LIBRARY) == ["anyof"]
-    assert not set(b.SET_LIBRARY) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES) | set(b.YET_MORE_LIBRARIES) | set(b.ONE_MORE_LIBRARY) | set(b.NEXT_LIBRARY))
-    entry = b.SET_LIBRARY["needleset"]
-    assert entry["parent"] == "anyof" and entry["sources"] == ["ss_needleset.hip"] and b._lib("needleset") is entry
-    assert os.path.exists(os.path.join(ROOT, "sliceslice-rs_amd", "csrc", "ss_needleset.hip"))
-    for name in ("service", "matches", "matches_batched", "lines", "nocase", "bounded", "inverted", "context", "anyof", "needleset"):
-        assert b._lib(name)["so"].endswith("libsliceslice_hip_%s.so" % name)
-    with pytest.raises(KeyError):
-        b._lib("no such library")
-    assert b.library_path_of("needleset") == entry["so"] == b.needleset_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_needleset.json" == os.path.basename(b.needleset_resources_path())
-    assert b._all_sources("needleset") == b._all_sources("anyof") + ["ss_needleset.hip"]
-    for h in ("needleset_kernels.hpp", "needleset_launch.hpp", "needleset_tables.hpp", os.path.join("..", "..", "include", "sliceslice_hip_needleset.h")):
-        assert h in b._HEADERS, h                                # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["needleset"][0] is ss.searcher.NEEDLESET_ABI and ss.searcher._FEATURES["needleset"][1] == "ss_needle_set_new"
-    product = ss.lib()
-    assert not product.has_needleset
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.needleset_build\(\)") as e:
-        ss.searcher._feature_lib(product, "needleset")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.needleset_build() as L:
-        assert ss.lib() is L and L.has_needleset and L.has_anyof and L.has_context and L.has_inverted and L.has_bounded and L.has_nocase
-        assert L.has_lines and L.has_matches and not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.anyof_build() as L:
-        assert not L.has_needleset
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("b.build_anyof(") < entry_point.index("b.build_needleset(force=True, verbose=True)") < entry_point.index("b.build_tuning(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_needleset.json" in ignored
-    assert "sixth table" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.14", 1)[1]            # why there are six tables
 
 
 def test_the_set_kernels_meet_their_bar_and_every_other_row_is_what_it_was():

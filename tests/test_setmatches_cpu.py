@@ -1,11 +1,10 @@
 """CPU checks of the occurrence calls of a needle set (include/sliceslice_hip_setmatches.h): the header, the ctypes table and the
 Rust module agree symbol by symbol; libsliceslice_hip_setmatches.so exports the needleset library's list plus four functions while
-every other library exports what it did; the seventh build table goes by name like the other six; the four occurrence kernels meet
+every other library exports what it did; the set's struct is shared through one internal header; the four occurrence kernels meet
 their resource bar and every row of the needleset record reappears unchanged; needle identity in csrc/needleset_tables.hpp - the
 ranks, the slots and set_each_at - passes a sweep against a brute-force memcmp loop in a stand-alone host program built with ASan
 and UBSan; the new methods of ss.NeedleSet are refused outside setmatches_build(); tools/grep_hip.py documents --frequencies and
 refuses what it should."""
-import ctypes
 import inspect
 import os
 import re
@@ -16,11 +15,11 @@ import pytest
 
 import sliceslice_rs_amd as ss
 from test_anyof_cpu import ANYOF
-from test_bindings_cpu import _c_class, _strip_c_comments, build_module as _build, exported as _exported, header_prototypes
+from test_bindings_cpu import build_module as _build, ctypes_class, exported as _exported, header_prototypes, rust_prototypes
 from test_bounded_cpu import BOUNDED, LINES, NOCASE, _grep
 from test_context_cpu import CONTEXT
 from test_inverted_cpu import INVERTED
-from test_needleset_cpu import NEEDLESET, needleset_prototypes
+from test_needleset_cpu import NEEDLESET
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -29,54 +28,23 @@ SETMATCHES = ["ss_needle_set_ranks", "ss_count_set_device", "ss_count_set_device
 
 
 # ---- header, ctypes table, Rust block -------------------------------------------------------------------------------------------
-def setmatches_prototypes():
-    text = _strip_c_comments(open(os.path.join(ROOT, "include", "sliceslice_hip_setmatches.h")).read())
-    text = "\n".join(l for l in text.splitlines() if not l.lstrip().startswith("#"))
-    protos = {}
-    for m in re.finditer(r"SS_API\s+(int|void)\s+(ss_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        args = []
-        for a in m.group(3).split(","):
-            typ = re.match(r"(.*?)([A-Za-z_][A-Za-z0-9_]*)$", a.strip()).group(1).strip()
-            args.append("u32" if typ == "unsigned" else _c_class(typ))
-        protos[m.group(2)] = ("i32" if m.group(1) == "int" else "void", args)
-    return protos
-
-
-def rust_block():
-    text = open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_setmatches.rs")).read()
-    block = re.sub(r"//[^\n]*", "", re.search(r'extern "C" \{(.*?)\n\}', text, flags=re.S).group(1))
-    cls = {"c_int": "i32", "c_uint": "u32", "u32": "u32", "usize": "usize", "u64": "u64"}
-    protos = {}
-    for m in re.finditer(r"fn\s+(ss_[a-z0-9_]+)\s*\((.*?)\)\s*(?:->\s*([^;]+))?;", block, flags=re.S):
-        types = [a.split(":", 1)[1].strip() for a in m.group(2).split(",") if a.strip()]
-        protos[m.group(1)] = (cls[m.group(3).strip()] if m.group(3) else "void", ["ptr" if t.startswith("*") else cls[t] for t in types])
-    return protos, text
-
-
 def test_header_ctypes_and_rust_agree():
-    c = setmatches_prototypes()
+    c = header_prototypes("sliceslice_hip_setmatches.h")
     assert sorted(c) == sorted(ss.searcher.SETMATCHES_ABI) == sorted(SETMATCHES)
     # (set, haystack, len, how, stream, ...): the count calls end in two pointers, find in two pointers, the capacity and the total
     assert c["ss_needle_set_ranks"] == ("i32", ["ptr", "ptr"])
     assert c["ss_count_set_device"] == c["ss_count_set_device_async"] == ("i32", ["ptr", "ptr", "usize", "u32", "ptr", "ptr", "ptr"])
     assert c["ss_find_all_set_device"] == ("i32", ["ptr", "ptr", "usize", "u32", "ptr", "ptr", "ptr", "u64", "ptr"])
-    r, rust = rust_block()
+    r, rust = rust_prototypes("hip_setmatches.rs"), open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_setmatches.rs")).read()
     assert r == c, (r, c)
     assert "use crate::hip_needleset::{ss_needle_set, NeedleSet};" in rust and "pub fn as_raw" in \
         open(os.path.join(ROOT, "sliceslice-rs_amd", "bindings", "rust", "hip_needleset.rs")).read()
-
-    def cls(t):
-        if t is None:
-            return "void"
-        if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
-            return "ptr"
-        return {ctypes.c_int: "i32", ctypes.c_uint: "u32", ctypes.c_uint32: "u32", ctypes.c_size_t: "u64", ctypes.c_uint64: "u64"}[t]
     for name, (res, args) in ss.searcher.SETMATCHES_ABI.items():
-        assert (cls(res), [cls(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
+        assert (ctypes_class(res), [ctypes_class(a) for a in args]) == (c[name][0], [a.replace("usize", "u64") for a in c[name][1]]), name
     for h in ("sliceslice_hip.h", "sliceslice_hip_matches.h", "sliceslice_hip_matches_batched.h", "sliceslice_hip_lines.h",
               "sliceslice_hip_nocase.h"):
         assert not set(c) & set(header_prototypes(h)), h
-    assert not set(c) & (set(needleset_prototypes()) | set(BOUNDED) | set(INVERTED) | set(CONTEXT) | set(ANYOF))
+    assert not set(c) & (set(header_prototypes("sliceslice_hip_needleset.h")) | set(BOUNDED) | set(INVERTED) | set(CONTEXT) | set(ANYOF))
     text = open(os.path.join(ROOT, "include", "sliceslice_hip_setmatches.h")).read()
     assert '#include "sliceslice_hip_needleset.h"' in text and "#define SS_BOUND" not in text and "#define SS_SET" not in text
     assert "typedef struct" not in text                         # the set's type is the needleset header's
@@ -117,42 +85,7 @@ def test_the_setmatches_library_exports_the_needleset_list_plus_four_and_the_oth
     assert os.path.basename(b.setmatches_library_path()) == "libsliceslice_hip_setmatches.so"
 
 
-def test_the_seventh_table_goes_by_name_like_the_others():
-    b = _build()
-    assert list(b.OCCURRENCE_LIBRARY) == ["setmatches"] and list(b.SET_LIBRARY) == ["needleset"]
-    assert not set(b.OCCURRENCE_LIBRARY) & (set(b.LIBRARIES) | set(b.MORE_LIBRARIES) | set(b.YET_MORE_LIBRARIES) | set(b.ONE_MORE_LIBRARY) |
-                                            set(b.NEXT_LIBRARY) | set(b.SET_LIBRARY))
-    entry = b.OCCURRENCE_LIBRARY["setmatches"]
-    assert entry["parent"] == "needleset" and entry["sources"] == ["ss_setmatches.hip"] and b._lib("setmatches") is entry
-    assert os.path.exists(os.path.join(CSRC, "ss_setmatches.hip"))
-    for name in ("service", "matches", "matches_batched", "lines", "nocase", "bounded", "inverted", "context", "anyof", "needleset", "setmatches"):
-        assert b._lib(name)["so"].endswith("libsliceslice_hip_%s.so" % name)
-    with pytest.raises(KeyError):
-        b._lib("no such library")
-    assert b.library_path_of("setmatches") == entry["so"] == b.setmatches_library_path()
-    assert os.path.basename(entry["resources"]) == "kernel_resources_setmatches.json" == os.path.basename(b.setmatches_resources_path())
-    assert b._all_sources("setmatches") == b._all_sources("needleset") + ["ss_setmatches.hip"]
-    for h in ("setmatches_kernels.hpp", "setmatches_launch.hpp", "needleset_host.hpp", "needleset_tables.hpp",
-              os.path.join("..", "..", "include", "sliceslice_hip_setmatches.h")):
-        assert h in b._HEADERS, h                                # a change to one of them rebuilds the objects
-    assert ss.searcher._FEATURES["setmatches"][0] is ss.searcher.SETMATCHES_ABI and ss.searcher._FEATURES["setmatches"][1] == "ss_count_set_device"
-    product = ss.lib()
-    assert not product.has_setmatches
-    with pytest.raises(ss.SlicesliceError, match=r"ss\.setmatches_build\(\)") as e:
-        ss.searcher._feature_lib(product, "setmatches")
-    assert e.value.code == ss.SS_ERR_ARGUMENT
-    with ss.setmatches_build() as L:
-        assert ss.lib() is L and L.has_setmatches and L.has_needleset and L.has_anyof and L.has_context and L.has_inverted and L.has_bounded
-        assert L.has_nocase and L.has_lines and L.has_matches and not L.has_matches_batched and not L.has_service
-    assert ss.lib() is product
-    with ss.needleset_build() as L:
-        assert not L.has_setmatches
-    entry_point = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert entry_point.index("b.build_needleset(") < entry_point.index("b.build_setmatches(force=True, verbose=True)") < entry_point.index("b.build_tuning(")
-    ignored = open(os.path.join(ROOT, ".gitignore")).read().split()
-    assert "sliceslice-rs_amd/csrc/kernel_resources_setmatches.json" in ignored
-    assert "seventh table" in open(os.path.join(ROOT, "DESIGN.md")).read().split("5.15", 1)[1]          # why there are seven tables
-    # the set's struct is shared by the two translation units through one internal header
+def test_the_sets_struct_is_shared_by_the_two_translation_units_through_one_internal_header():
     host = open(os.path.join(CSRC, "needleset_host.hpp")).read()
     assert "struct ss_needle_set {" in host
     for tu in ("ss_needleset.hip", "ss_setmatches.hip"):
