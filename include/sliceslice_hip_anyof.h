@@ -54,7 +54,8 @@
  *
  * Out of scope: ONE scan that filters for all needles in a single pass over the haystack (the follow-up that this header makes
  * measurable: sliceslice_hip_needleset.h compiles the needles into a set and selects the same lines in one scan); async and capturable forms; batched, plan, sharded, service and host / file forms; -m; -o with several needles; a
- * `how` per needle; regular expressions; multi-byte terminators.
+ * `how` per needle; regular expressions; multi-byte terminators; the text of the lines (sliceslice_hip_output.h gathers and
+ * numbers the records of any line call on the device).
  */
 #ifndef SLICESLICE_HIP_ANYOF_H
 #define SLICESLICE_HIP_ANYOF_H

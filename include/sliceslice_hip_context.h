@@ -12,7 +12,7 @@
  *            over s in S of [max(1, s - b), min(N, s + a)], each line once, in ascending order.
  *   kind     1 for a line of S (grep prints `number:`), 0 for a context line (grep prints `number-`).
  *   --       grep's separator stands wherever two consecutive output numbers differ by more than 1; the library returns no
- *            separators, the caller derives them.
+ *            separators, the caller derives them (sliceslice_hip_output.h writes them, with the lines' text, on the device).
  *   before, after   any uint64_t value: the additions and subtractions saturate, 2^64 - 1 means "to the ends of the view".
  *   An empty S gives an empty output whatever b and a are.
  * Bytes outside the view never count: neither a delimiter just in front of a misaligned view nor one just behind its end.

@@ -43,7 +43,8 @@
  *
  * Out of scope: async and capturable forms; batched, plan, sharded, service and host / file forms; -m; -o; a `how` per needle;
  * regular expressions; multi-byte terminators; an occurrence (non-line) form for sets (sliceslice_hip_setmatches.h has it, in a
- * library of its own).
+ * library of its own); the text of the lines (sliceslice_hip_output.h gathers and numbers the records of any line call on the
+ * device).
  */
 #ifndef SLICESLICE_HIP_NEEDLESET_H
 #define SLICESLICE_HIP_NEEDLESET_H

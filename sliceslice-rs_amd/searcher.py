@@ -194,6 +194,16 @@ DISJOINT_ABI = {
     "ss_replace_device": (_int, [_vp, _vp, _sz, _uint, _vp, _sz, _vp, _vp, _u64, _pu64, _pu64]),
 }
 DISJOINT_BLOCK = 4096               # SS_DISJOINT_BLOCK: offsets per workgroup of the selection kernels
+# include/sliceslice_hip_output.h: grep's output written on the device (the gather of any list of ranges, with line numbers,
+# terminators and `--` separators) - libsliceslice_hip_output.so only (the disjoint library's objects plus the output kernels)
+OUTPUT_ABI = {
+    "ss_format_lines_device": (_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _u64, _int, _uint, _vp, _vp, _u64, _vp, _pu64]),
+    "ss_gather_ranges_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _int, _vp, _vp, _u64, _vp, _pu64]),
+    "ss_grep_lines_device": (_int, [_vp, _vp, _sz, _int, _uint, _u64, _u64, _uint, _vp, _vp, _u64, _pu64, _pu64, _pu64]),
+}
+SS_OUTPUT_NUMBER, SS_OUTPUT_SEPARATOR = 1, 2
+OUTPUT_BLOCK = 4096                 # SS_OUTPUT_BLOCK: records per workgroup of the size passes
+OUTPUT_CHUNK = 16384                # SS_OUTPUT_CHUNK: output bytes per workgroup of the copy pass
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -329,6 +339,9 @@ _FEATURES = {
                  "the non-overlapping calls (count_disjoint / find_all_disjoint / find_all_disjoint_into / replace / "
                  "select_disjoint / select_disjoint_into) are not part of this library: they live in "
                  "libsliceslice_hip_disjoint.so - create the searcher inside `with ss.disjoint_build():`"),
+    "output": (OUTPUT_ABI, "ss_format_lines_device",
+               "the output calls (format_lines / format_lines_into / gather_ranges / grep / grep_anyof / NeedleSet.grep) are not part "
+               "of this library: they live in libsliceslice_hip_output.so - create the searcher inside `with ss.output_build():`"),
 }
 
 
@@ -485,6 +498,15 @@ class disjoint_build(_library_build):
     ``whole_word`` - and ``ss.select_disjoint`` / ``ss.select_disjoint_into``, the greedy selection over any ascending list of
     offsets)."""
     name = "disjoint"
+
+
+class output_build(_library_build):
+    """libsliceslice_hip_output.so: the disjoint library plus GREP'S OUTPUT written on the device
+    (include/sliceslice_hip_output.h: ``ss.format_lines`` / ``ss.format_lines_into`` - the text of a list of records with line
+    numbers, ``:`` / ``-``, terminators and ``--`` separators - ``ss.gather_ranges``, the gather of any list of ranges,
+    ``grep`` of searchers created inside the block - ``grep -n -A / -B / -C -F``'s stdout as a device tensor; it takes
+    ``ignore_case``, ``whole_word``, ``whole_line`` and ``invert`` - and ``ss.grep_anyof`` / ``NeedleSet.grep``)."""
+    name = "output"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -888,6 +910,122 @@ def select_disjoint(offsets, n, capacity=None, stream=None):
     return out[:min(int(capacity), total)]
 
 
+# The output calls (include/sliceslice_hip_output.h): functions of the module, since no searcher owns them.
+def _scratch_searcher(L):
+    """The searcher of library `L` that a call which needs one for the device and its scratch only is handed."""
+    global _lib
+    s = _UNION_SEARCHERS.get(id(L))
+    if s is None:
+        saved, _lib = _lib, L
+        try:
+            s = _UNION_SEARCHERS.setdefault(id(L), DynamicHipSearcher.new(b""))
+        finally:
+            _lib = saved
+    return s
+
+
+def _terminator_byte(terminator):
+    """The terminator of the output calls: None (-1, none) or one byte as ``_delimiter_byte`` takes it."""
+    return -1 if terminator is None else _delimiter_byte(terminator)
+
+
+def _device_kinds(kind, dev):
+    """The kinds of format_lines as a uint8 device tensor (a 1-byte tensor on the device is taken as it is)."""
+    import torch
+    if _is_tensor(kind):
+        if kind.dtype.itemsize != 1:
+            raise TypeError("kinds are 1-byte integers")
+        return kind.contiguous().to(dev).view(torch.uint8).reshape(-1)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(kind, dtype=np.uint8)).reshape(-1).copy()).to(dev)
+
+
+def _output_flags(number, line_numbers, separators):
+    return (SS_OUTPUT_NUMBER if (number is not None if line_numbers is None else line_numbers) else 0) | (SS_OUTPUT_SEPARATOR if separators else 0)
+
+
+def _format_into(L, haystack, begin, end, number, kind, terminator, flags, d_out, d_starts, stream, gather=False):
+    """One ss_format_lines_device (gather: ss_gather_ranges_device) call of library `L`; returns *out_len."""
+    import torch
+    L = _feature_lib(L, "output")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    dev = t.device if t is not None else next((x.device for x in (begin, d_out) if _is_tensor(x) and x.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    s = _scratch_searcher(L)
+    out_len = _u64(0)
+    with _on_device_of(t if t is not None else d_out):
+        b, e = _device_numbers(begin, dev).reshape(-1), _device_numbers(end, dev).reshape(-1)
+        n = _device_numbers(number, dev).reshape(-1) if number is not None else None
+        k = _device_kinds(kind, dev) if kind is not None else None
+        if any(x is not None and x.numel() != b.numel() for x in (e, n, k)):
+            raise ValueError("begin, end, number and kind hold one entry per record")
+        if d_starts is not None and d_starts.numel() < b.numel() + 1:
+            raise ValueError("d_starts holds count + 1 entries")
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None and x.numel() else None for x in (b, e, n, k, d_out, d_starts)]
+        capacity = d_out.numel() if d_out is not None else 0
+        if gather:
+            _check(L.ss_gather_ranges_device(s._h, ptr, length, p[0], p[1], b.numel(), _terminator_byte(terminator), st, p[4], capacity, p[5],
+                                             ctypes.byref(out_len)), L)
+        else:
+            _check(L.ss_format_lines_device(s._h, ptr, length, p[0], p[1], p[2], p[3], b.numel(), _terminator_byte(terminator), int(flags), st,
+                                            p[4], capacity, p[5], ctypes.byref(out_len)), L)
+    return out_len.value
+
+
+def _format(L, haystack, begin, end, number, kind, terminator, flags, stream, gather=False, return_starts=False):
+    """The count-only call, then the sized one: the output as a uint8 device tensor (return_starts: and the count + 1 starts)."""
+    import torch
+    _feature_lib(L, "output")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    dev = t.device if t is not None else (begin.device if _is_tensor(begin) and begin.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    hay = t if t is not None else (ptr, length)
+    begin, end = _device_numbers(begin, dev).reshape(-1), _device_numbers(end, dev).reshape(-1)
+    number = _device_numbers(number, dev).reshape(-1) if number is not None else None
+    kind = _device_kinds(kind, dev) if kind is not None else None
+    starts = torch.empty(begin.numel() + 1, dtype=torch.int64, device=dev) if return_starts else None
+    total = _format_into(L, hay, begin, end, number, kind, terminator, flags, None, starts, stream, gather)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    if total:
+        _format_into(L, hay, begin, end, number, kind, terminator, flags, out[:total], None, stream, gather)
+    return (out[:total], starts) if return_starts else out[:total]
+
+
+def format_lines_into(haystack, begin, end, d_out, number=None, kind=None, delimiter=b"\n", line_numbers=None, separators=False, d_starts=None,
+                      stream=None):
+    """ss_format_lines_device into the caller's 1-byte device tensor ``d_out`` (capacity = its length; None: the length only) and,
+    where given, the count + 1 starts into the 8-byte device tensor ``d_starts``; returns the length of the output.  A ``d_out``
+    that is too short is left untouched.  Arguments as ``format_lines``.  Inside ``with ss.output_build():``."""
+    return _format_into(lib(), haystack, begin, end, number, kind, delimiter, _output_flags(number, line_numbers, separators), d_out, d_starts, stream)
+
+
+def format_lines(haystack, begin, end, number=None, kind=None, delimiter=b"\n", line_numbers=None, separators=False, stream=None):
+    """The text of the records (begin, end, number, kind) of ``haystack`` - what the line calls return; sequences, arrays or device
+    tensors - as one uint8 device tensor: for every record ``--`` and the delimiter where ``separators`` is set and its number lies
+    more than 1 above the one before, its number and ``:`` (kind != 0, or no kind) or ``-`` where ``line_numbers`` is set (None: set
+    exactly when numbers are given), the bytes [begin, end) clamped to the haystack, and the delimiter (None: none) -
+    ``grep -n -A / -B / -C``'s stdout (ss_format_lines_device: counted first, then sized exactly).  Any list is formatted: records
+    may overlap, repeat or descend.  Inside ``with ss.output_build():``."""
+    return _format(lib(), haystack, begin, end, number, kind, delimiter, _output_flags(number, line_numbers, separators), stream)
+
+
+def gather_ranges(haystack, begin, end, terminator=None, return_starts=False, stream=None):
+    """The bytes [begin[i], end[i]) of ``haystack``, clamped to it, one range after the other and each followed by ``terminator``
+    (one byte; None: none), as one uint8 device tensor (ss_gather_ranges_device) - what ``grep -o`` and ``sed -n 'Np'`` print from
+    a list of ranges.  return_starts: also the int64 device tensor of the count + 1 output offsets at which the ranges begin, the
+    last of them the length.  Inside ``with ss.output_build():``."""
+    return _format(lib(), haystack, begin, end, None, None, terminator, 0, stream, gather=True, return_starts=return_starts)
+
+
+def grep_anyof(searchers, haystack, before=0, after=0, delimiter=b"\n", line_numbers=False, stream=None, ignore_case=False, whole_word=False,
+               whole_line=False, invert=False):
+    """``grep -e A -e B`` 's stdout as a uint8 device tensor: ``find_lines_anyof`` followed by ``format_lines`` (separators exactly
+    when ``before`` or ``after`` is non-zero, as in grep).  Searchers made inside ``with ss.output_build():``."""
+    searchers = list(searchers)
+    L = _feature_lib(getattr(searchers[0], "_inner", searchers[0])._L if searchers else lib(), "output")
+    begin, end, number, kind = find_lines_anyof(searchers, haystack, before, after, delimiter, None, stream, ignore_case, whole_word, whole_line,
+                                                invert)
+    return _format(L, haystack, begin, end, number, kind, delimiter, _output_flags(number, line_numbers, bool(before or after)), stream)
+
+
 class NeedleSet:
     """A compiled set of needles (ss_needle_set_new, inside ``with ss.needleset_build():``) on the current device.  Its line calls
     select what ``ss.count_lines_anyof`` / ``ss.find_lines_anyof`` select for searchers of the same needles, in one pass over
@@ -955,6 +1093,15 @@ class NeedleSet:
         total, _ = self.find_lines_into(hay, p[0], p[1], p[2], p[3], capacity, **kw)
         k = min(int(capacity), total)
         return out[0, :k], out[1, :k], out[2, :k], kind[:k]
+
+    def grep(self, haystack, before=0, after=0, delimiter=b"\n", line_numbers=False, whole_word=False, whole_line=False, invert=False,
+             stream=None):
+        """``grep -f FILE``'s stdout as a uint8 device tensor: ``find_lines`` followed by ``ss.format_lines`` (separators exactly when
+        ``before`` or ``after`` is non-zero) - byte for byte what ``ss.grep_anyof`` gives for searchers of the same needles.  Sets
+        made inside ``with ss.output_build():``."""
+        L = _feature_lib(self._L, "output")
+        begin, end, number, kind = self.find_lines(haystack, before, after, delimiter, whole_word, whole_line, invert, None, stream)
+        return _format(L, haystack, begin, end, number, kind, delimiter, _output_flags(number, line_numbers, bool(before or after)), stream)
 
     # -- every occurrence, per needle (include/sliceslice_hip_setmatches.h; inside ``with ss.setmatches_build():``) --------------
     def _occurrence_how(self, whole_word):
@@ -1355,6 +1502,31 @@ class DynamicHipSearcher:
         """ss_lines_around_device into the caller's device tensors (each may be None); returns the size of the output."""
         return _lines_around_into(self, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream)
 
+    # -- grep's output (libsliceslice_hip_output.so: searchers made inside `with ss.output_build():`) -----------------------------
+    def grep(self, haystack, before=0, after=0, delimiter=b"\n", line_numbers=False, stream=None, ignore_case=False, whole_word=False,
+             whole_line=False, invert=False):
+        """uint8 tensor on the haystack's device: what ``grep -F needle`` writes to stdout - the selected lines and their ``before`` /
+        ``after`` context lines, each closed by the delimiter, with ``number:`` / ``number-`` in front where ``line_numbers`` is
+        set and ``--`` between groups exactly when ``before`` or ``after`` is non-zero, as in grep (ss_grep_lines_device: sized with
+        a first call, then written).  The flags are ``find_lines_context``'s."""
+        import torch
+        L = _feature_lib(self._L, "output")
+        ptr, length, t = self._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        flags = (SS_OUTPUT_NUMBER if line_numbers else 0) | (SS_OUTPUT_SEPARATOR if before or after else 0)
+        how, d = _context_how(ignore_case, whole_word, whole_line, invert), _delimiter_byte(delimiter)
+        b, a = _context_amount(before, "before"), _context_amount(after, "after")
+        out_len, lines, selected = _u64(0), _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            self._ck(L.ss_grep_lines_device(self._h, ptr, length, d, how, b, a, flags, st, None, 0, ctypes.byref(out_len), ctypes.byref(lines),
+                                            ctypes.byref(selected)))
+            out = torch.empty(max(out_len.value, 1), dtype=torch.uint8, device=dev)
+            if out_len.value:
+                self._ck(L.ss_grep_lines_device(self._h, ptr, length, d, how, b, a, flags, st, out.data_ptr(), out_len.value, ctypes.byref(out_len),
+                                                ctypes.byref(lines), ctypes.byref(selected)))
+        return out[:min(out_len.value, out.numel() if out_len.value else 0)]
+
     # -- tuning / measurement hooks ------------------------------------------------------------------
     @property
     def filter(self):
@@ -1518,6 +1690,10 @@ class MemchrHipSearcher:
 
     def lines_around_into(self, haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before=0, after=0, delimiter=b"\n", stream=None):
         return self._inner.lines_around_into(haystack, numbers, d_begin, d_end, d_number, d_kind, capacity, before, after, delimiter, stream)
+
+    def grep(self, haystack, before=0, after=0, delimiter=b"\n", line_numbers=False, stream=None, ignore_case=False, whole_word=False,
+             whole_line=False, invert=False):
+        return self._inner.grep(haystack, before, after, delimiter, line_numbers, stream, ignore_case, whole_word, whole_line, invert)
 
 
 def shard_range(length, needle_len, nranks, rank):

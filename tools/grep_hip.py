@@ -46,7 +46,12 @@ file's own bytes).  Without -o, --count and --offsets stay what they were: every
 ./grep_hip.py --replace <text> [-i] [-w] <needle> <file> - the file with every non-overlapping occurrence replaced by <text>, to
 stdout (sed 's/needle/text/g' for a fixed string, bytes.replace; ss_replace_device: the substituted bytes are made on the device).
 Both refuse -x, -v, -A / -B / -C, --count-lines, --lines, --frequencies and -e / -f: the non-overlapping selection is about the
-occurrences of one needle; --replace refuses the empty needle."""
+occurrences of one needle; --replace refuses the empty needle.
+./grep_hip.py --device-output --lines [-i] [-w | -x] [-v] [-A NUM] [-B NUM] [-C NUM] [--one-pass] (<needle> | (-e <pattern>)... [-f
+<patterns file>]) <file> - what --lines prints, byte for byte, with the text made ON THE DEVICE: the lines are gathered, numbered
+(`number:` / `number-`), terminated and separated by `--` there, and the finished text comes to the host in one copy
+(libsliceslice_hip_output.so: ss_grep_lines_device for one needle, ss_find_lines_anyof_device or ss_find_lines_set_device followed by
+ss_format_lines_device for several).  --device-output goes with --lines only; without it nothing changes."""
 import os
 import sys
 
@@ -126,6 +131,38 @@ def context_lines(searcher, data, before, after, ignore_case=False, invert=False
     return b"".join(out)
 
 
+def device_output(argv, patterns, context, fold, word, line, invert):
+    """--device-output --lines: grep -n's stdout from the output library, one device-to-host copy of the finished text."""
+    import torch
+    rest = [a for a in argv if a not in ("--device-output", "-i", "--ignore-case", "-w", "--word-regexp", "-x", "--line-regexp", "-v", "--invert-match")]
+    args, flags = [a for a in rest if not a.startswith("--")], {a for a in rest if a.startswith("--")}
+    one_pass = "--one-pass" in flags
+    if flags - {"--one-pass"} != {"--lines"} or len(args) != (1 if patterns else 2) or (one_pass and not patterns):
+        raise SystemExit("./grep_hip.py --device-output --lines [-i] [-w | -x] [-v] [-A NUM] [-B NUM] [-C NUM] [--one-pass] "
+                         "(<needle> | (-e <pattern>)... [-f <patterns file>]) <file>: --device-output writes the text that --lines "
+                         "prints, and --one-pass compiles several patterns")
+    needles = patterns or [args[0].encode()]
+    if word and line:
+        raise SystemExit("./grep_hip.py: -w and -x exclude each other (a call keeps whole words or whole lines)")
+    if (word or line) and not all(needles):
+        raise SystemExit("./grep_hip.py: -w / -x with the empty needle is out of scope (it has no neighbour bytes to test)")
+    if len(needles) > ss.ANYOF_MAX_NEEDLES:
+        raise SystemExit("./grep_hip.py: %d patterns; a call takes %d (-e / -f)" % (len(needles), ss.ANYOF_MAX_NEEDLES))
+    data = open(args[-1], "rb").read()
+    hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+    before, after = min(context.get("before", 0), 2 ** 64 - 1), min(context.get("after", 0), 2 ** 64 - 1)
+    with ss.output_build():
+        if one_pass:
+            out = ss.NeedleSet(needles, ignore_case=fold).grep(hay, before, after, line_numbers=True, whole_word=word, whole_line=line, invert=invert)
+        elif patterns:
+            searchers = [ss.DynamicHipSearcher.new_nocase(p) if fold else ss.DynamicHipSearcher.new(p) for p in needles]
+            out = ss.grep_anyof(searchers, hay, before, after, line_numbers=True, ignore_case=fold, whole_word=word, whole_line=line, invert=invert)
+        else:
+            searcher = ss.DynamicHipSearcher.new_nocase(needles[0]) if fold else ss.DynamicHipSearcher.new(needles[0])
+            out = searcher.grep(hay, before, after, line_numbers=True, ignore_case=fold, whole_word=word, whole_line=line, invert=invert)
+    sys.stdout.buffer.write(out.cpu().numpy().tobytes())
+
+
 def main():
     argv, patterns, context, replacement = [], [], {}, None
     it = iter(sys.argv[1:])
@@ -156,6 +193,8 @@ def main():
     line = "-x" in argv or "--line-regexp" in argv
     invert = "-v" in argv or "--invert-match" in argv
     only = "-o" in argv or "--only-matching" in argv
+    if "--device-output" in argv and not (only or "--replace" in argv or "--frequencies" in argv):
+        return device_output(argv, patterns, context, fold, word, line, invert)
     if only or "--replace" in argv:
         what = "--replace" if "--replace" in argv else "-o"
         usage = ("./grep_hip.py -o (--count | --offsets) [-i] [-w] <needle> <file>\n"
