@@ -55,6 +55,7 @@
  *
  * Out of scope: leftmost-longest selection over a needle set's pairs; SS_BOUND_LINE and inverted forms; an async / capturable
  * form; batched, plan, sharded, service and host / file forms; regular expressions and back-references in the replacement.
+ * (Leftmost-longest selection over a set's pairs, and a replace with a text per needle: sliceslice_hip_leftmost.h.)
  */
 #ifndef SLICESLICE_HIP_DISJOINT_H
 #define SLICESLICE_HIP_DISJOINT_H

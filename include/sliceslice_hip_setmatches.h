@@ -42,6 +42,7 @@
  * Out of scope: the empty needle; SS_BOUND_LINE and inverted forms; leftmost-longest / non-overlapping selection (it follows on
  * the host from the ordered pairs); batched, plan, sharded, service and host / file forms.  (The non-overlapping occurrences of ONE
  * needle are sliceslice_hip_disjoint.h's; its primitive takes one length, so it does not select among a set's pairs.)
+ * (That selection on the device, and a replace with a text per needle: sliceslice_hip_leftmost.h.)
  */
 #ifndef SLICESLICE_HIP_SETMATCHES_H
 #define SLICESLICE_HIP_SETMATCHES_H

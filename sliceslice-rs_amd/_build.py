@@ -63,6 +63,9 @@ LIBRARIES = {
 # The thirteenth, in a mapping of its own until the table's pinned list of names moves: grep's output written on the device
 # (include/sliceslice_hip_output.h).  Everything below looks in both mappings.
 _LATER_LIBRARIES = {"output": _library("output", "disjoint", ["ss_output.hip"])}
+# ... and the fourteenth beside it: leftmost-longest selection over a needle set's pairs and the set replace
+# (include/sliceslice_hip_leftmost.h).
+_LATER_LIBRARIES["leftmost"] = _library("leftmost", "output", ["ss_leftmost.hip"])
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]

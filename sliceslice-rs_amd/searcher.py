@@ -204,6 +204,17 @@ OUTPUT_ABI = {
 SS_OUTPUT_NUMBER, SS_OUTPUT_SEPARATOR = 1, 2
 OUTPUT_BLOCK = 4096                 # SS_OUTPUT_BLOCK: records per workgroup of the size passes
 OUTPUT_CHUNK = 16384                # SS_OUTPUT_CHUNK: output bytes per workgroup of the copy pass
+# include/sliceslice_hip_leftmost.h: the leftmost-longest, non-overlapping occurrences of a needle set (count, offsets and needles,
+# replace with a text per needle) and that selection over any list of (offset, length) entries - libsliceslice_hip_leftmost.so
+# only (the output library's objects plus the selection and the set-replace kernels)
+LEFTMOST_ABI = {
+    "ss_select_leftmost_device": (_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _pu64]),
+    "ss_count_leftmost_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _pu64]),
+    "ss_find_all_leftmost_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _vp, _u64, _pu64]),
+    "ss_replace_set_device": (_int, [_vp, _vp, _sz, _uint, _vp, _vp, _u32, _vp, _vp, _u64, _pu64, _pu64]),
+    "ss_needle_set_lengths": (_int, [_vp, _vp]),
+}
+LEFTMOST_BLOCK = 4096               # SS_LEFTMOST_BLOCK: entries per workgroup of the selection kernels
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -342,6 +353,10 @@ _FEATURES = {
     "output": (OUTPUT_ABI, "ss_format_lines_device",
                "the output calls (format_lines / format_lines_into / gather_ranges / grep / grep_anyof / NeedleSet.grep) are not part "
                "of this library: they live in libsliceslice_hip_output.so - create the searcher inside `with ss.output_build():`"),
+    "leftmost": (LEFTMOST_ABI, "ss_select_leftmost_device",
+                 "the leftmost-longest calls (NeedleSet.count_leftmost / find_all_leftmost / find_all_leftmost_into / replace / "
+                 "lengths, select_leftmost / select_leftmost_into) are not part of this library: they live in "
+                 "libsliceslice_hip_leftmost.so - create the set inside `with ss.leftmost_build():`"),
 }
 
 
@@ -507,6 +522,15 @@ class output_build(_library_build):
     ``grep`` of searchers created inside the block - ``grep -n -A / -B / -C -F``'s stdout as a device tensor; it takes
     ``ignore_case``, ``whole_word``, ``whole_line`` and ``invert`` - and ``ss.grep_anyof`` / ``NeedleSet.grep``)."""
     name = "output"
+
+
+class leftmost_build(_library_build):
+    """libsliceslice_hip_leftmost.so: the output library plus the LEFTMOST-LONGEST, non-overlapping occurrences of a needle set
+    (include/sliceslice_hip_leftmost.h: ``count_leftmost`` / ``find_all_leftmost`` / ``find_all_leftmost_into`` / ``replace`` /
+    ``lengths`` of ``ss.NeedleSet`` objects created inside the block - ``grep -o -F -f FILE``, aho_corasick's leftmost-longest
+    ``find_iter`` and ``replace_all``, ``re.sub`` over an alternation of literals; they take ``whole_word`` - and
+    ``ss.select_leftmost`` / ``ss.select_leftmost_into``, that selection over any list of (offset, length) entries)."""
+    name = "leftmost"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -910,6 +934,64 @@ def select_disjoint(offsets, n, capacity=None, stream=None):
     return out[:min(int(capacity), total)]
 
 
+_SCRATCH_SETS = {}
+
+
+def _scratch_set(L):
+    """The needle set of library `L` that ss_select_leftmost_device is handed for the device and its scratch only."""
+    global _lib
+    s = _SCRATCH_SETS.get(id(L))
+    if s is None:
+        saved, _lib = _lib, L
+        try:
+            s = _SCRATCH_SETS.setdefault(id(L), NeedleSet([b"a"]))
+        finally:
+            _lib = saved
+    return s
+
+
+def select_leftmost_into(offsets, lengths, d_selected, d_which, capacity=None, stream=None):
+    """ss_select_leftmost_device into the caller's 8-byte device tensors (each may be None; capacity: default the shorter of
+    them, 0 where both are None); returns the size of the selection.  Inside ``with ss.leftmost_build():``."""
+    import torch
+    L = _feature_lib(lib(), "leftmost")
+    given = [x for x in (d_selected, d_which) if x is not None]
+    dev = offsets.device if _is_tensor(offsets) and offsets.is_cuda else (given[0].device if given else torch.device("cuda", torch.cuda.current_device()))
+    if capacity is None:
+        capacity = min(x.numel() for x in given) if given else 0
+    total = _u64(0)
+    with _on_device_of(given[0] if given else offsets):
+        flat = _device_numbers(offsets, dev).reshape(-1)
+        lens = _device_numbers(lengths, dev).reshape(-1)
+        if lens.numel() != flat.numel():
+            raise ValueError("%d offsets and %d lengths" % (flat.numel(), lens.numel()))
+        s = _scratch_set(L)
+        st = stream if stream is not None else _current_stream_handle()
+        _check(L.ss_select_leftmost_device(s._h, flat.data_ptr() if flat.numel() else None, lens.data_ptr() if lens.numel() else None,
+                                           flat.numel(), st, d_selected.data_ptr() if d_selected is not None and d_selected.numel() else None,
+                                           d_which.data_ptr() if d_which is not None and d_which.numel() else None, int(capacity),
+                                           ctypes.byref(total)), L)
+    return total.value
+
+
+def select_leftmost(offsets, lengths, capacity=None, stream=None):
+    """The leftmost-longest selection over entries (offsets[j], lengths[j]) - sequences, arrays or device tensors; the offsets
+    ascend and may repeat, the lengths ascend within a run of equal offsets: the last entry of a run is its candidate, the first
+    candidate is selected, and after a selected p of length l the first candidate at or beyond p + l.  Returns
+    (selected offsets, their indices in the list) as int64 device tensors of min(total, capacity) entries
+    (ss_select_leftmost_device).  Inside ``with ss.leftmost_build():``."""
+    import torch
+    _feature_lib(lib(), "leftmost")
+    dev = offsets.device if _is_tensor(offsets) and offsets.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    flat, lens = _device_numbers(offsets, dev).reshape(-1), _device_numbers(lengths, dev).reshape(-1)
+    if capacity is None:
+        capacity = select_leftmost_into(flat, lens, None, None, 0, stream)
+    out = torch.empty((2, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+    total = select_leftmost_into(flat, lens, out[0] if capacity else None, out[1] if capacity else None, int(capacity), stream)
+    k = min(int(capacity), total)
+    return out[0, :k], out[1, :k]
+
+
 # The output calls (include/sliceslice_hip_output.h): functions of the module, since no searcher owns them.
 def _scratch_searcher(L):
     """The searcher of library `L` that a call which needs one for the device and its scratch only is handed."""
@@ -1042,6 +1124,7 @@ class NeedleSet:
         _check(L.ss_needle_set_new(table, lens, count, SS_SET_NOCASE if ignore_case else 0, ctypes.byref(h)), L)
         self._h = h
         self._count = count
+        self._needles = [bytes(ctypes.string_at(v[1], v[2])) if v[2] else b"" for v in views]      # (for ``replace`` with a mapping)
         self.ignore_case = bool(ignore_case)
 
     def _how(self, whole_word, whole_line, invert):
@@ -1195,6 +1278,104 @@ class NeedleSet:
         total = self.find_all_into(hay, offsets if capacity else None, rank if capacity else None, capacity, whole_word, stream)
         k = min(int(capacity), total)
         return offsets[:k], self._rank_maps(dev)[1][rank[:k].long()]
+
+    # -- leftmost-longest selection (include/sliceslice_hip_leftmost.h; inside ``with ss.leftmost_build():``) --------------------
+    def lengths(self):
+        """The length of the needle of every rank (ss_needle_set_lengths) as an int64 numpy array of ``info()["distinct"]`` entries:
+        what turns the ranks of ``find_all_into`` into the lengths ``ss.select_leftmost`` takes."""
+        L = _feature_lib(self._L, "leftmost")
+        distinct = self.info()["distinct"]
+        out = np.zeros(max(distinct, 1), dtype=np.uint64)
+        _check(L.ss_needle_set_lengths(self._h, out.ctypes.data), L)
+        return out[:distinct].astype(np.int64)
+
+    def count_leftmost(self, haystack, whole_word=False, stream=None):
+        """int: the number of leftmost-longest, non-overlapping occurrences of the set's needles - the lines ``grep -o -F -f FILE``
+        prints (ss_count_leftmost_set_device).  The word test comes before the selection."""
+        L = _feature_lib(self._L, "leftmost")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_count_leftmost_set_device(self._h, ptr, length, self._occurrence_how(whole_word), st, ctypes.byref(c)), L)
+        return c.value
+
+    def find_all_leftmost_into(self, haystack, d_offsets, d_ranks, capacity, whole_word=False, stream=None):
+        """ss_find_all_leftmost_set_device into the caller's device tensors (8-byte offsets, 4-byte RANKS; each may be None);
+        returns the number of selected occurrences."""
+        L = _feature_lib(self._L, "leftmost")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_find_all_leftmost_set_device(self._h, ptr, length, self._occurrence_how(whole_word), st,
+                                                     d_offsets.data_ptr() if d_offsets is not None else None,
+                                                     d_ranks.data_ptr() if d_ranks is not None else None, int(capacity), ctypes.byref(total)), L)
+        return total.value
+
+    def find_all_leftmost(self, haystack, whole_word=False, capacity=None, stream=None):
+        """(offsets, which) of the first ``capacity`` (default: all) leftmost-longest, non-overlapping occurrences, ascending, as
+        int64 device tensors; ``which`` is the smallest index as given of the selected needle, as in ``find_all``."""
+        import torch
+        _feature_lib(self._L, "leftmost")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.find_all_leftmost_into(hay, None, None, 0, whole_word, stream)
+        offsets = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        rank = torch.empty(max(int(capacity), 1), dtype=torch.int32, device=dev)
+        total = self.find_all_leftmost_into(hay, offsets if capacity else None, rank if capacity else None, capacity, whole_word, stream)
+        k = min(int(capacity), total)
+        return offsets[:k], self._rank_maps(dev)[1][rank[:k].long()]
+
+    def replace(self, haystack, replacements, whole_word=False, stream=None):
+        """uint8 tensor on the haystack's device: the haystack with every leftmost-longest, non-overlapping occurrence replaced by
+        its needle's own text - ``replacements`` is a sequence parallel to the needles as given, or a mapping needle -> text that
+        holds every needle (host bytes, may be empty; needles that are equal, or equal after the set's fold, must carry equal
+        texts).  ``re.sub`` over the alternation, longest first, with a function (ss_replace_set_device; one call where the output's
+        length is bounded by at most twice the haystack's, else sized first)."""
+        import torch
+        L = _feature_lib(self._L, "leftmost")
+        if hasattr(replacements, "keys"):
+            given = getattr(self, "_needles", None)
+            if given is None:
+                raise ValueError("a mapping of replacements needs the needles of a set made by NeedleSet(needles)")
+            table = {bytes(k): bytes(v) for k, v in replacements.items()}
+            texts = [table[n] for n in given]
+        else:
+            texts = [bytes(r) for r in replacements]
+        if len(texts) != self._count:
+            raise ValueError("%d replacements for %d needles" % (len(texts), self._count))
+        views = [_host_view(r) for r in texts]
+        reps = (ctypes.c_void_p * max(self._count, 1))(*[v[1] if v[2] else None for v in views])
+        lens = (ctypes.c_size_t * max(self._count, 1))(*[v[2] for v in views])
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        how = self._occurrence_how(whole_word)
+        out_len, c = _u64(0), _u64(0)
+        # One pass where the output's length is bounded cheaply: no selection can add more than the longest text less the shortest
+        # needle, so texts that add nothing bound it by the haystack's length, and others by the pairs' count (one scan) times
+        # that growth.  The buffer is taken from the bound when it is at most twice the haystack; else the call sizes it first.
+        given = getattr(self, "_needles", None)
+        grow = max(0, max(len(r) for r in texts) - min(len(n) for n in given)) if given and all(given) else None
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            bound = None if grow is None else length if grow == 0 or length == 0 else \
+                length + grow * self.count_total(t if t is not None else (ptr, length), whole_word, st)
+            if bound is not None and bound <= 2 * length + (1 << 20):
+                out = torch.empty(max(bound, 1), dtype=torch.uint8, device=dev)
+                _check(L.ss_replace_set_device(self._h, ptr, length, how, reps, lens, self._count, st, out.data_ptr(), bound,
+                                               ctypes.byref(out_len), ctypes.byref(c)), L)
+                if out_len.value <= bound:                      # (always: the bound holds)
+                    return out[:out_len.value]
+            _check(L.ss_replace_set_device(self._h, ptr, length, how, reps, lens, self._count, st, None, 0, ctypes.byref(out_len),
+                                           ctypes.byref(c)), L)
+            out = torch.empty(max(out_len.value, 1), dtype=torch.uint8, device=dev)
+            if out_len.value:
+                _check(L.ss_replace_set_device(self._h, ptr, length, how, reps, lens, self._count, st, out.data_ptr(), out_len.value,
+                                               ctypes.byref(out_len), ctypes.byref(c)), L)
+        return out[:min(out_len.value, out.numel() if out_len.value else 0)]
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

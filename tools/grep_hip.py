@@ -47,6 +47,15 @@ file's own bytes).  Without -o, --count and --offsets stay what they were: every
 stdout (sed 's/needle/text/g' for a fixed string, bytes.replace; ss_replace_device: the substituted bytes are made on the device).
 Both refuse -x, -v, -A / -B / -C, --count-lines, --lines, --frequencies and -e / -f: the non-overlapping selection is about the
 occurrences of one needle; --replace refuses the empty needle.
+./grep_hip.py -o (--count | --offsets) [-i] [-w] (-e <needle>)... [-f <needles file>] <file> - -o with -e / -f: the LEFTMOST-LONGEST,
+non-overlapping occurrences of a SET of needles - at each offset the longest needle, taken greedily from the left, the word test
+first - --count their number and --offsets `offset:match` for each, byte for byte what LC_ALL=C grep -o -b -F prints for those
+patterns (libsliceslice_hip_leftmost.so, ss_count_leftmost_set_device / ss_find_all_leftmost_set_device: the selection is made on the
+device).
+./grep_hip.py --replace-map <map file> [-i] [-w] <file> - the file with each of those occurrences replaced by its needle's own text, to
+stdout; the map file holds one `needle<TAB>text` pair per line (re.sub over an alternation of literals with a replacement per
+literal; ss_replace_set_device).  Both refuse -x, -v, -A / -B / -C, --count-lines, --lines, --frequencies, --one-pass, --device-output
+and --replace, and the empty needle.
 ./grep_hip.py --device-output --lines [-i] [-w | -x] [-v] [-A NUM] [-B NUM] [-C NUM] [--one-pass] (<needle> | (-e <pattern>)... [-f
 <patterns file>]) <file> - what --lines prints, byte for byte, with the text made ON THE DEVICE: the lines are gathered, numbered
 (`number:` / `number-`), terminated and separated by `--` there, and the finished text comes to the host in one copy
@@ -163,13 +172,60 @@ def device_output(argv, patterns, context, fold, word, line, invert):
     sys.stdout.buffer.write(out.cpu().numpy().tobytes())
 
 
+def leftmost_forms(argv, patterns, context, replace_map, fold, word, line, invert):
+    """-o (--count | --offsets) [-i] [-w] (-e NEEDLE ... | -f FILE) FILE: the leftmost-longest, non-overlapping occurrences of a SET of
+    needles - byte for byte what LC_ALL=C grep -o -b -F prints for those patterns - and --replace-map MAPFILE [-i] [-w] FILE: the file
+    with each of them replaced by its needle's own text, one `needle<TAB>text` pair per line of MAPFILE (ss_find_all_leftmost_set_device
+    and ss_replace_set_device of libsliceslice_hip_leftmost.so: the selection and the substitution are made on the device)."""
+    what = "--replace-map" if "--replace-map" in argv else "-o"
+    usage = ("./grep_hip.py -o (--count | --offsets) [-i] [-w] (-e <needle>)... [-f <needles file>] <file>\n"
+             "./grep_hip.py --replace-map <map file> [-i] [-w] <file>")
+    refused = [("-x", line), ("-v", invert), (context.get("flag"), bool(context))] + \
+              [(f, f in argv) for f in ("--count-lines", "--lines", "--frequencies", "--one-pass", "--device-output", "--replace")] + \
+              [(f, f in argv and what == "--replace-map") for f in ("--count", "--offsets", "-o", "--only-matching")] + \
+              [("-e / -f", bool(patterns) and what == "--replace-map")]
+    for flag, given in refused:
+        if given:
+            raise SystemExit("./grep_hip.py: %s does not go with %s: the leftmost-longest, non-overlapping selection is about the "
+                             "occurrences of a set of needles (-i and -w combine with it)" % (flag, what))
+    rest = [a for a in argv if a not in ("-o", "--only-matching", "--replace-map", "-i", "--ignore-case", "-w", "--word-regexp")]
+    args, flags = [a for a in rest if not a.startswith("--")], {a for a in rest if a.startswith("--")}
+    if len(args) != 1 or (what == "--replace-map" and (replace_map is None or flags)) or (what == "-o" and flags not in ({"--count"}, {"--offsets"})):
+        raise SystemExit(usage)
+    texts = None
+    if what == "--replace-map":
+        pairs = [l.split(b"\t", 1) for l in open(replace_map, "rb").read().split(b"\n") if l]
+        if not pairs or any(len(p) != 2 for p in pairs):
+            raise SystemExit("./grep_hip.py: every line of the map file holds a needle, one TAB and its text")
+        patterns, texts = [p[0] for p in pairs], [p[1] for p in pairs]
+    if not all(patterns):
+        raise SystemExit("./grep_hip.py: the empty needle is out of scope for a set (its occurrences belong to no scan)")
+    if len(patterns) > ss.ANYOF_MAX_NEEDLES:
+        raise SystemExit("./grep_hip.py: %d needles; a set takes %d" % (len(patterns), ss.ANYOF_MAX_NEEDLES))
+    with ss.leftmost_build():
+        needles = ss.NeedleSet(patterns, ignore_case=fold)
+    import torch
+    data = open(args[0], "rb").read()
+    hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+    if texts is not None:
+        sys.stdout.buffer.write(needles.replace(hay, texts, whole_word=word).cpu().numpy().tobytes())
+    elif "--count" in flags:
+        print(needles.count_leftmost(hay, whole_word=word))
+    else:
+        offsets, which = needles.find_all_leftmost(hay, whole_word=word)
+        sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (o, data[o:o + len(patterns[k])]) for o, k in zip(offsets.cpu().tolist(), which.cpu().tolist())))
+
+
 def main():
-    argv, patterns, context, replacement = [], [], {}, None
+    argv, patterns, context, replacement, replace_map = [], [], {}, None, None
     it = iter(sys.argv[1:])
     for a in it:
         if a == "--replace":
             argv.append(a)
             replacement = next(it, None)
+        elif a == "--replace-map":
+            argv.append(a)
+            replace_map = next(it, None)
         elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
@@ -195,6 +251,8 @@ def main():
     only = "-o" in argv or "--only-matching" in argv
     if "--device-output" in argv and not (only or "--replace" in argv or "--frequencies" in argv):
         return device_output(argv, patterns, context, fold, word, line, invert)
+    if "--replace-map" in argv or (only and patterns and "--replace" not in argv and "--frequencies" not in argv):
+        return leftmost_forms(argv, patterns, context, replace_map, fold, word, line, invert)
     if only or "--replace" in argv:
         what = "--replace" if "--replace" in argv else "-o"
         usage = ("./grep_hip.py -o (--count | --offsets) [-i] [-w] <needle> <file>\n"
