@@ -2,7 +2,8 @@
 
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES below (service, matches, matches_batched, lines, nocase, bounded,
-                                  inverted, context, anyof, needleset, setmatches, disjoint) and of the mapping under it (output): the
+                                  inverted, context, anyof, needleset, setmatches, disjoint) and of the mappings under it (output,
+                                  leftmost, masked): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -66,6 +67,9 @@ _LATER_LIBRARIES = {"output": _library("output", "disjoint", ["ss_output.hip"])}
 # ... and the fourteenth beside it: leftmost-longest selection over a needle set's pairs and the set replace
 # (include/sliceslice_hip_leftmost.h).
 _LATER_LIBRARIES["leftmost"] = _library("leftmost", "output", ["ss_leftmost.hip"])
+# ... and the fifteenth, in a third mapping because the two above are pinned name by name: byte patterns with wildcards and per-byte
+# masks (include/sliceslice_hip_masked.h).
+_LATEST_LIBRARIES = {"masked": _library("masked", "leftmost", ["ss_masked.hip"])}
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
@@ -238,7 +242,7 @@ def build(force=False, verbose=False):
 
 def _lib(name):
     """The entry of library `name` (KeyError: there is none)."""
-    return LIBRARIES[name] if name in LIBRARIES else _LATER_LIBRARIES[name]
+    return LIBRARIES[name] if name in LIBRARIES else _LATEST_LIBRARIES[name] if name in _LATEST_LIBRARIES else _LATER_LIBRARIES[name]
 
 
 def _all_sources(name):
@@ -282,7 +286,7 @@ def _wrappers(name):
     return named
 
 
-for _name in list(LIBRARIES) + list(_LATER_LIBRARIES):
+for _name in list(LIBRARIES) + list(_LATER_LIBRARIES) + list(_LATEST_LIBRARIES):
     globals().update(_wrappers(_name))
 
 

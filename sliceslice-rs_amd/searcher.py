@@ -215,6 +215,23 @@ LEFTMOST_ABI = {
     "ss_needle_set_lengths": (_int, [_vp, _vp]),
 }
 LEFTMOST_BLOCK = 4096               # SS_LEFTMOST_BLOCK: entries per workgroup of the selection kernels
+# include/sliceslice_hip_masked.h: byte patterns with wildcards and per-byte masks, searched in ONE pass (occurrences and matching
+# lines) - libsliceslice_hip_masked.so only (the leftmost library's objects plus the masked scan)
+MASKED_ABI = {
+    "ss_masked_new": (_int, [_vp, _vp, _sz, _pvp]),
+    "ss_masked_free": (None, [_vp]),
+    "ss_masked_info": (_int, [_vp, _int, _vp]),
+    "ss_masked_parse_hex": (_int, [ctypes.c_char_p, _vp, _vp, _sz, _psz]),
+    "ss_masked_choose_filter": (_int, [_vp, _vp, _sz, _vp, _psz, _psz]),
+    "ss_count_masked_device": (_int, [_vp, _vp, _sz, _vp, _pu64]),
+    "ss_count_masked_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_masked_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_masked_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64]),
+    "ss_find_lines_masked_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
+MASKED_MAX_LEN = 4096               # SS_MASKED_MAX_LEN: bytes of a pattern
+# ss_masked_stats: eight 64-bit words, in this order
+MASKED_STATS = ("n", "anchor", "distance", "full", "partial", "wild", "accepts_delimiter", "reserved")
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -357,6 +374,10 @@ _FEATURES = {
                  "the leftmost-longest calls (NeedleSet.count_leftmost / find_all_leftmost / find_all_leftmost_into / replace / "
                  "lengths, select_leftmost / select_leftmost_into) are not part of this library: they live in "
                  "libsliceslice_hip_leftmost.so - create the set inside `with ss.leftmost_build():`"),
+    "masked": (MASKED_ABI, "ss_masked_new",
+               "the masked-pattern calls (ss.MaskedPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
+               "find_lines_into / info, ss.parse_hex, ss.masked_choose_filter) are not part of this library: they live in "
+               "libsliceslice_hip_masked.so - create the pattern inside `with ss.masked_build():`"),
 }
 
 
@@ -531,6 +552,15 @@ class leftmost_build(_library_build):
     ``find_iter`` and ``replace_all``, ``re.sub`` over an alternation of literals; they take ``whole_word`` - and
     ``ss.select_leftmost`` / ``ss.select_leftmost_into``, that selection over any list of (offset, length) entries)."""
     name = "leftmost"
+
+
+class masked_build(_library_build):
+    """libsliceslice_hip_masked.so: the leftmost library plus BYTE PATTERNS WITH WILDCARDS AND PER-BYTE MASKS, searched in one pass
+    (include/sliceslice_hip_masked.h: ``ss.MaskedPattern(value, mask)`` / ``.from_hex("48 8b ?? 4?")`` /
+    ``.from_bytes(b"intel", ignore_case=True)`` with ``count`` / ``count_async`` / ``find_all`` / ``find_all_into`` /
+    ``count_lines`` / ``find_lines`` / ``find_lines_into`` / ``info`` of patterns created inside the block, and ``ss.parse_hex`` /
+    ``ss.masked_choose_filter``, which are host only)."""
+    name = "masked"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -1382,6 +1412,169 @@ class NeedleSet:
         L = getattr(self, "_L", None)
         if h and L is not None and _lib is not None:
             L.ss_needle_set_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_hex(text):
+    """(value, mask) bytes of a hex pattern such as ``"48 8b ?? 4?"`` (ss_masked_parse_hex: tokens of two characters separated by
+    optional blanks, each character a hex digit of either case or ``?``).  Host only; inside ``with ss.masked_build():``."""
+    L = _feature_lib(lib(), "masked")
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    if b"\0" in raw:
+        raise SlicesliceError(SS_ERR_ARGUMENT, "ss_masked_parse_hex: column %d: a NUL is neither a hex digit nor '?'" % (raw.index(b"\0") + 1))
+    n = _sz(0)
+    _check(L.ss_masked_parse_hex(raw, None, None, 0, ctypes.byref(n)), L)
+    value, mask = np.zeros(max(n.value, 1), dtype=np.uint8), np.zeros(max(n.value, 1), dtype=np.uint8)
+    _check(L.ss_masked_parse_hex(raw, value.ctypes.data, mask.ctypes.data, n.value, ctypes.byref(n)), L)
+    return value[:n.value].tobytes(), mask[:n.value].tobytes()
+
+
+def masked_choose_filter(value, mask=None, hist=None):
+    """(anchor, distance) of ss_masked_choose_filter: the two pattern positions the masked kernel tests in registers (distance 0:
+    one).  ``hist``: 256 counts of the haystack's bytes, or None for the static costs.  Host only; inside ``with ss.masked_build():``."""
+    L = _feature_lib(lib(), "masked")
+    v = np.frombuffer(bytes(value), dtype=np.uint8)
+    m = np.frombuffer(bytes(mask), dtype=np.uint8) if mask is not None else None
+    if m is not None and m.size != v.size:
+        raise ValueError("value holds %d bytes and mask %d" % (v.size, m.size))
+    h = np.ascontiguousarray(hist, dtype=np.uint64) if hist is not None else None
+    if h is not None and h.size != 256:
+        raise ValueError("a histogram holds 256 counts, got %d" % h.size)
+    a, d = _sz(0), _sz(0)
+    _check(L.ss_masked_choose_filter(v.ctypes.data if v.size else None, m.ctypes.data if m is not None and m.size else None, v.size,
+                                     h.ctypes.data if h is not None else None, ctypes.byref(a), ctypes.byref(d)), L)
+    return a.value, d.value
+
+
+class MaskedPattern:
+    """A fixed-length byte pattern with a mask per byte (ss_masked_new, inside ``with ss.masked_build():``) on the current device:
+    position p matches when ``(hay[p + i] & mask[i]) == value[i]`` for every i (include/sliceslice_hip_masked.h has the rule).
+    ``mask=None`` means all 0xFF.  The methods follow ``NeedleSet``'s forms."""
+
+    def __init__(self, value, mask=None):
+        self._h = None
+        self._L = L = _feature_lib(lib(), "masked")
+        v = np.frombuffer(bytes(value), dtype=np.uint8)
+        m = np.frombuffer(bytes(mask), dtype=np.uint8) if mask is not None else None
+        if m is not None and m.size != v.size:
+            raise ValueError("value holds %d bytes and mask %d" % (v.size, m.size))
+        h = ctypes.c_void_p()
+        _check(L.ss_masked_new(v.ctypes.data if v.size else None, m.ctypes.data if m is not None and m.size else None, v.size, ctypes.byref(h)), L)
+        self._h = h
+        self.mask = m.tobytes() if m is not None else b"\xff" * v.size
+        self.value = bytes(a & b for a, b in zip(v.tobytes(), self.mask))
+
+    @classmethod
+    def from_hex(cls, text):
+        """The pattern of a YARA / ClamAV style hex string: ``MaskedPattern.from_hex("48 8b ?? 4?")``."""
+        return cls(*parse_hex(text))
+
+    @classmethod
+    def from_bytes(cls, data, ignore_case=False):
+        """The pattern of a literal; ``ignore_case``: the letters A-Z / a-z get mask 0xDF, which is exact for them and touches
+        no other byte."""
+        data = bytes(data)
+        mask = bytes(0xDF if ignore_case and (0x41 <= b <= 0x5A or 0x61 <= b <= 0x7A) else 0xFF for b in data)
+        return cls(data, mask)
+
+    def info(self, delimiter=None):
+        """dict of ss_masked_info: n, anchor, distance, full, partial, wild, accepts_delimiter (for ``delimiter``, if one is given)."""
+        words = (ctypes.c_uint64 * len(MASKED_STATS))()
+        _check(self._L.ss_masked_info(self._h, -1 if delimiter is None else _delimiter_byte(delimiter), words), self._L)
+        d = dict(zip(MASKED_STATS, (int(w) for w in words)))
+        del d["reserved"]
+        return d
+
+    def count(self, haystack, stream=None):
+        """int: the occurrences, overlapping ones included (ss_count_masked_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_masked_device(self._h, ptr, length, st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def count_async(self, haystack, out=None, stream=None):
+        """ss_count_masked_device_async into ``out`` (a one-element int64 device tensor, made when None) and returns it:
+        stream-ordered, no wait, capturable into a graph."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if out is None:
+            out = torch.empty(1, dtype=torch.int64, device=t.device if t is not None else torch.device("cuda", torch.cuda.current_device()))
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_masked_device_async(self._h, ptr, length, st, out.data_ptr()), self._L)
+        return out
+
+    def find_all_into(self, haystack, out, capacity=None, stream=None):
+        """ss_find_all_masked_device into the caller's 8-byte device tensor (None with capacity 0); returns the total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if capacity is None:
+            capacity = out.numel() if out is not None else 0
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_find_all_masked_device(self._h, ptr, length, st, out.data_ptr() if out is not None else None, int(capacity),
+                                                     ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_all(self, haystack, capacity=None, stream=None):
+        """int64 device tensor: the first ``capacity`` (default: all, counted first) occurrence offsets, ascending."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.find_all_into(hay, None, 0, stream)
+        out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        total = self.find_all_into(hay, out if capacity else None, int(capacity), stream)
+        return out[:min(int(capacity), total)]
+
+    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+        """int: the lines that hold an occurrence wholly inside them (ss_count_lines_masked_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_lines_masked_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+        """ss_find_lines_masked_device into the caller's 8-byte device tensors (each may be None); returns the total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+            _check(self._L.ss_find_lines_masked_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
+                                                       ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number) int64 device tensors of the first ``capacity`` (default: all, counted first) matching lines,
+        ascending - the records of ``DynamicHipSearcher.find_lines``."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.count_lines(hay, delimiter, stream)
+        out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        p = [out[k] if capacity else None for k in range(3)]
+        total = self.find_lines_into(hay, p[0], p[1], p[2], int(capacity), delimiter, stream)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k], out[2, :k]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        L = getattr(self, "_L", None)
+        if h and L is not None and _lib is not None:
+            L.ss_masked_free(h)
 
     def __del__(self):
         try:

@@ -60,7 +60,12 @@ and --replace, and the empty needle.
 <patterns file>]) <file> - what --lines prints, byte for byte, with the text made ON THE DEVICE: the lines are gathered, numbered
 (`number:` / `number-`), terminated and separated by `--` there, and the finished text comes to the host in one copy
 (libsliceslice_hip_output.so: ss_grep_lines_device for one needle, ss_find_lines_anyof_device or ss_find_lines_set_device followed by
-ss_format_lines_device for several).  --device-output goes with --lines only; without it nothing changes."""
+ss_format_lines_device for several).  --device-output goes with --lines only; without it nothing changes.
+./grep_hip.py --hex '<pattern>' (--count | --offsets | --count-lines | --lines) [--device-output] <file> - a byte pattern with
+wildcards and per-byte masks in ONE pass (libsliceslice_hip_masked.so, include/sliceslice_hip_masked.h): tokens of two characters,
+each a hex digit or `?`, such as '48 8b ?? 4?'.  --count prints the number of (overlapping) occurrences, --offsets one offset per
+line, --count-lines the number of lines that hold an occurrence wholly inside them and --lines those lines as `number:line`;
+with --device-output the text of --lines is made on the device (ss_format_lines_device).  Every other flag is refused."""
 import os
 import sys
 
@@ -216,8 +221,40 @@ def leftmost_forms(argv, patterns, context, replace_map, fold, word, line, inver
         sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (o, data[o:o + len(patterns[k])]) for o, k in zip(offsets.cpu().tolist(), which.cpu().tolist())))
 
 
+def hex_forms(argv, hex_pattern, patterns, context, replacement, replace_map):
+    """--hex PATTERN (--count | --offsets | --count-lines | --lines) [--device-output] FILE: the masked-pattern calls."""
+    import torch
+    usage = "./grep_hip.py --hex '<pattern>' (--count | --offsets | --count-lines | --lines) [--device-output] <file>"
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    device = "--device-output" in flags
+    modes = [f for f in flags if f != "--device-output"]
+    if hex_pattern is None or len(args) != 1 or len(modes) != 1 or modes[0] not in ("--count", "--offsets", "--count-lines", "--lines") or \
+            patterns or context or replacement is not None or replace_map is not None or (device and modes[0] != "--lines"):
+        raise SystemExit(usage + ": --hex takes one pattern, one of the four modes and no other flag (--device-output with --lines)")
+    data = open(args[0], "rb").read()
+    hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+    with ss.masked_build():
+        try:
+            pat = ss.MaskedPattern.from_hex(hex_pattern)
+        except ss.SlicesliceError as e:
+            raise SystemExit("./grep_hip.py: --hex %r: %s" % (hex_pattern, e))
+        if modes[0] == "--count":
+            print(pat.count(hay))
+        elif modes[0] == "--offsets":
+            sys.stdout.buffer.write(b"".join(b"%d\n" % o for o in pat.find_all(hay).cpu().tolist()))
+        elif modes[0] == "--count-lines":
+            print(pat.count_lines(hay))
+        else:
+            begin, end, number = pat.find_lines(hay)
+            if device:
+                sys.stdout.buffer.write(ss.format_lines(hay, begin, end, number, line_numbers=True).cpu().numpy().tobytes())
+            else:
+                sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (n, data[b:e]) for b, e, n in zip(begin.cpu().tolist(), end.cpu().tolist(), number.cpu().tolist())))
+
+
 def main():
     argv, patterns, context, replacement, replace_map = [], [], {}, None, None
+    hex_pattern, hex_given = None, False
     it = iter(sys.argv[1:])
     for a in it:
         if a == "--replace":
@@ -226,6 +263,8 @@ def main():
         elif a == "--replace-map":
             argv.append(a)
             replace_map = next(it, None)
+        elif a == "--hex":
+            hex_given, hex_pattern = True, next(it, None)
         elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
@@ -244,6 +283,8 @@ def main():
             context["flag"] = flag
         else:
             argv.append(a)
+    if hex_given:
+        return hex_forms(argv, hex_pattern, patterns, context, replacement, replace_map)
     fold = "-i" in argv or "--ignore-case" in argv
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
