@@ -3,7 +3,7 @@
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES below (service, matches, matches_batched, lines, nocase, bounded,
                                   inverted, context, anyof, needleset, setmatches, disjoint) and of the mappings under it (output,
-                                  leftmost, masked): the
+                                  leftmost, masked, classes): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -70,6 +70,8 @@ _LATER_LIBRARIES["leftmost"] = _library("leftmost", "output", ["ss_leftmost.hip"
 # ... and the fifteenth, in a third mapping because the two above are pinned name by name: byte patterns with wildcards and per-byte
 # masks (include/sliceslice_hip_masked.h).
 _LATEST_LIBRARIES = {"masked": _library("masked", "leftmost", ["ss_masked.hip"])}
+# ... and the sixteenth below it: fixed-length patterns of byte classes (include/sliceslice_hip_classes.h).
+_LATEST_LIBRARIES["classes"] = _library("classes", "masked", ["ss_classes.hip"])
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]

@@ -232,6 +232,25 @@ MASKED_ABI = {
 MASKED_MAX_LEN = 4096               # SS_MASKED_MAX_LEN: bytes of a pattern
 # ss_masked_stats: eight 64-bit words, in this order
 MASKED_STATS = ("n", "anchor", "distance", "full", "partial", "wild", "accepts_delimiter", "reserved")
+# include/sliceslice_hip_classes.h: fixed-length patterns of byte classes ([0-9], \\w), searched in ONE pass (occurrences and matching
+# lines) - libsliceslice_hip_classes.so only (the masked library's objects plus the class scan)
+CLASSES_ABI = {
+    "ss_classes_new": (_int, [_vp, _sz, _pvp]),
+    "ss_classes_free": (None, [_vp]),
+    "ss_classes_info": (_int, [_vp, _int, _vp]),
+    "ss_classes_parse": (_int, [ctypes.c_char_p, _int, _vp, _sz, _psz]),
+    "ss_classes_cover": (_int, [_vp, _sz, _vp, _vp]),
+    "ss_count_classes_device": (_int, [_vp, _vp, _sz, _vp, _pu64]),
+    "ss_count_classes_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_classes_device": (_int, [_vp, _vp, _sz, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_classes_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64]),
+    "ss_find_lines_classes_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
+CLASSES_MAX_LEN = 4096              # SS_CLASSES_MAX_LEN: positions of a pattern
+CLASSES_MAX_INEXACT = 1024          # SS_CLASSES_MAX_INEXACT: positions whose set is not exactly its cover
+CLASSES_MAX_DISTINCT = 64           # SS_CLASSES_MAX_DISTINCT: distinct sets among them
+# ss_classes_stats: eight 64-bit words, in this order
+CLASSES_STATS = ("n", "anchor", "distance", "single", "masked", "inexact", "distinct", "accepts_delimiter")
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -378,6 +397,10 @@ _FEATURES = {
                "the masked-pattern calls (ss.MaskedPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
                "find_lines_into / info, ss.parse_hex, ss.masked_choose_filter) are not part of this library: they live in "
                "libsliceslice_hip_masked.so - create the pattern inside `with ss.masked_build():`"),
+    "classes": (CLASSES_ABI, "ss_classes_new",
+                "the byte-class calls (ss.ClassPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
+                "find_lines_into / info, ss.parse_classes, ss.classes_cover) are not part of this library: they live in "
+                "libsliceslice_hip_classes.so - create the pattern inside `with ss.classes_build():`"),
 }
 
 
@@ -561,6 +584,14 @@ class masked_build(_library_build):
     ``count_lines`` / ``find_lines`` / ``find_lines_into`` / ``info`` of patterns created inside the block, and ``ss.parse_hex`` /
     ``ss.masked_choose_filter``, which are host only)."""
     name = "masked"
+
+
+class classes_build(_library_build):
+    """libsliceslice_hip_classes.so: the masked library plus FIXED-LENGTH PATTERNS OF BYTE CLASSES, searched in one pass
+    (include/sliceslice_hip_classes.h: ``ss.ClassPattern(r"[0-9A-F]{4}H")`` / ``.from_sets`` / ``.from_masked`` / ``.from_bytes``
+    with ``count`` / ``count_async`` / ``find_all`` / ``find_all_into`` / ``count_lines`` / ``find_lines`` / ``find_lines_into`` /
+    ``info`` of patterns created inside the block, and ``ss.parse_classes`` / ``ss.classes_cover``, which are host only)."""
+    name = "classes"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -1575,6 +1606,187 @@ class MaskedPattern:
         L = getattr(self, "_L", None)
         if h and L is not None and _lib is not None:
             L.ss_masked_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _class_sets(sets):
+    """``sets`` as a contiguous (n, 4) uint64 array: 256 bits per position, byte b is bit b & 63 of word b >> 6."""
+    a = np.ascontiguousarray(sets, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("sets are an (n, 4) array of 64-bit words, got shape %r" % (a.shape,))
+    return a
+
+
+def parse_classes(text, ignore_case=False):
+    """(n, 4) uint64 array: the set of every position of a pattern such as ``r"[0-9A-F]{4}H"`` (ss_classes_parse: the strict subset
+    of Python ``re`` byte patterns under re.DOTALL that include/sliceslice_hip_classes.h lays down).  Host only; inside
+    ``with ss.classes_build():``."""
+    L = _feature_lib(lib(), "classes")
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    if b"\0" in raw:
+        raise SlicesliceError(SS_ERR_ARGUMENT, "ss_classes_parse: column %d: a NUL ends the text: write \\x00" % (raw.index(b"\0") + 1))
+    n = _sz(0)
+    _check(L.ss_classes_parse(raw, int(bool(ignore_case)), None, 0, ctypes.byref(n)), L)
+    sets = np.zeros((max(n.value, 1), 4), dtype=np.uint64)
+    _check(L.ss_classes_parse(raw, int(bool(ignore_case)), sets.ctypes.data, n.value, ctypes.byref(n)), L)
+    return sets[:n.value]
+
+
+def classes_cover(sets):
+    """(value, mask) bytes: the tightest cover of every position's set (ss_classes_cover).  Host only; inside
+    ``with ss.classes_build():``."""
+    L = _feature_lib(lib(), "classes")
+    a = _class_sets(sets)
+    value, mask = np.zeros(max(len(a), 1), dtype=np.uint8), np.zeros(max(len(a), 1), dtype=np.uint8)
+    _check(L.ss_classes_cover(a.ctypes.data if len(a) else None, len(a), value.ctypes.data, mask.ctypes.data), L)
+    return value[:len(a)].tobytes(), mask[:len(a)].tobytes()
+
+
+class ClassPattern:
+    """A fixed-length pattern whose positions are sets of bytes (ss_classes_new, inside ``with ss.classes_build():``) on the current
+    device: position p matches when ``hay[p + i]`` is in set i for every i (include/sliceslice_hip_classes.h has the rule and the
+    pattern language of ``text``).  The methods are ``MaskedPattern``'s."""
+
+    def __init__(self, text, ignore_case=False):
+        self._h = None
+        self._L = _feature_lib(lib(), "classes")
+        self._make(parse_classes(text, ignore_case))
+
+    def _make(self, sets):
+        L = self._L
+        h = ctypes.c_void_p()
+        _check(L.ss_classes_new(sets.ctypes.data if len(sets) else None, len(sets), ctypes.byref(h)), L)
+        self._h = h
+        self.sets = sets
+
+    @classmethod
+    def from_sets(cls, sets):
+        """The pattern of an (n, 4) array of 64-bit words: 256 bits per position."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._L = _feature_lib(lib(), "classes")
+        self._make(_class_sets(sets).copy())
+        return self
+
+    @classmethod
+    def from_masked(cls, value, mask=None):
+        """The pattern that accepts at position i the bytes b with ``(b & mask[i]) == (value[i] & mask[i])``: what
+        ``MaskedPattern(value, mask)`` accepts.  No position of it is inexact."""
+        v = np.frombuffer(bytes(value), dtype=np.uint8)
+        m = np.frombuffer(bytes(mask), dtype=np.uint8) if mask is not None else np.full(v.size, 0xFF, dtype=np.uint8)
+        if m.size != v.size:
+            raise ValueError("value holds %d bytes and mask %d" % (v.size, m.size))
+        b = np.arange(256, dtype=np.uint8)
+        member = (b[None, :] & m[:, None]) == (v & m)[:, None]
+        bits = np.packbits(member, axis=1, bitorder="little")
+        return cls.from_sets(np.ascontiguousarray(bits).view("<u8").astype(np.uint64).reshape(v.size, 4))
+
+    @classmethod
+    def from_bytes(cls, data, ignore_case=False):
+        """The pattern of a literal; ``ignore_case``: the letters A-Z / a-z accept either case."""
+        data = bytes(data)
+        return cls.from_masked(data, bytes(0xDF if ignore_case and (0x41 <= b <= 0x5A or 0x61 <= b <= 0x7A) else 0xFF for b in data))
+
+    def __len__(self):
+        return len(self.sets)
+
+    def info(self, delimiter=None):
+        """dict of ss_classes_info: n, anchor, distance, single, masked, inexact, distinct, accepts_delimiter (for ``delimiter``, if
+        one is given)."""
+        words = (ctypes.c_uint64 * len(CLASSES_STATS))()
+        _check(self._L.ss_classes_info(self._h, -1 if delimiter is None else _delimiter_byte(delimiter), words), self._L)
+        return dict(zip(CLASSES_STATS, (int(w) for w in words)))
+
+    def count(self, haystack, stream=None):
+        """int: the occurrences, overlapping ones included (ss_count_classes_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_classes_device(self._h, ptr, length, st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def count_async(self, haystack, out=None, stream=None):
+        """ss_count_classes_device_async into ``out`` (a one-element int64 device tensor, made when None) and returns it:
+        stream-ordered, no wait, capturable into a graph."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if out is None:
+            out = torch.empty(1, dtype=torch.int64, device=t.device if t is not None else torch.device("cuda", torch.cuda.current_device()))
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_classes_device_async(self._h, ptr, length, st, out.data_ptr()), self._L)
+        return out
+
+    def find_all_into(self, haystack, out, capacity=None, stream=None):
+        """ss_find_all_classes_device into the caller's 8-byte device tensor (None with capacity 0); returns the total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if capacity is None:
+            capacity = out.numel() if out is not None else 0
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_find_all_classes_device(self._h, ptr, length, st, out.data_ptr() if out is not None else None, int(capacity),
+                                                      ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_all(self, haystack, capacity=None, stream=None):
+        """int64 device tensor: the first ``capacity`` (default: all, counted first) occurrence offsets, ascending."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.find_all_into(hay, None, 0, stream)
+        out = torch.empty(max(int(capacity), 1), dtype=torch.int64, device=dev)
+        total = self.find_all_into(hay, out if capacity else None, int(capacity), stream)
+        return out[:min(int(capacity), total)]
+
+    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+        """int: the lines that hold an occurrence wholly inside them (ss_count_lines_classes_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_lines_classes_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+        """ss_find_lines_classes_device into the caller's 8-byte device tensors (each may be None); returns the total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+            _check(self._L.ss_find_lines_classes_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
+                                                        ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number) int64 device tensors of the first ``capacity`` (default: all, counted first) matching lines,
+        ascending - the records of ``DynamicHipSearcher.find_lines``."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.count_lines(hay, delimiter, stream)
+        out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        p = [out[k] if capacity else None for k in range(3)]
+        total = self.find_lines_into(hay, p[0], p[1], p[2], int(capacity), delimiter, stream)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k], out[2, :k]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        L = getattr(self, "_L", None)
+        if h and L is not None and _lib is not None:
+            L.ss_classes_free(h)
 
     def __del__(self):
         try:

@@ -65,7 +65,12 @@ ss_format_lines_device for several).  --device-output goes with --lines only; wi
 wildcards and per-byte masks in ONE pass (libsliceslice_hip_masked.so, include/sliceslice_hip_masked.h): tokens of two characters,
 each a hex digit or `?`, such as '48 8b ?? 4?'.  --count prints the number of (overlapping) occurrences, --offsets one offset per
 line, --count-lines the number of lines that hold an occurrence wholly inside them and --lines those lines as `number:line`;
-with --device-output the text of --lines is made on the device (ss_format_lines_device).  Every other flag is refused."""
+with --device-output the text of --lines is made on the device (ss_format_lines_device).  Every other flag is refused.
+./grep_hip.py --classes '<pattern>' [-i] (--count | --offsets | --count-lines | --lines) [--device-output] <file> - a fixed-length
+pattern of byte classes in ONE pass (libsliceslice_hip_classes.so, include/sliceslice_hip_classes.h, which has the pattern language:
+a strict subset of Python `re` byte patterns under re.DOTALL), such as '[0-9A-F]{4}H', '\\d\\d:\\d\\d' or '[^a-z]the[^a-z]'.  The four modes
+and --device-output are those of --hex; -i is re.I.  Every other flag is refused, and a pattern the language refuses is reported
+with its column."""
 import os
 import sys
 
@@ -238,23 +243,54 @@ def hex_forms(argv, hex_pattern, patterns, context, replacement, replace_map):
             pat = ss.MaskedPattern.from_hex(hex_pattern)
         except ss.SlicesliceError as e:
             raise SystemExit("./grep_hip.py: --hex %r: %s" % (hex_pattern, e))
-        if modes[0] == "--count":
-            print(pat.count(hay))
-        elif modes[0] == "--offsets":
-            sys.stdout.buffer.write(b"".join(b"%d\n" % o for o in pat.find_all(hay).cpu().tolist()))
-        elif modes[0] == "--count-lines":
-            print(pat.count_lines(hay))
+        print_pattern_mode(pat, modes[0], device, hay, data)
+
+
+def print_pattern_mode(pat, mode, device, hay, data):
+    """What --count / --offsets / --count-lines / --lines print for a MaskedPattern or a ClassPattern (inside its library's block)."""
+    if mode == "--count":
+        print(pat.count(hay))
+    elif mode == "--offsets":
+        sys.stdout.buffer.write(b"".join(b"%d\n" % o for o in pat.find_all(hay).cpu().tolist()))
+    elif mode == "--count-lines":
+        print(pat.count_lines(hay))
+    else:
+        begin, end, number = pat.find_lines(hay)
+        if device:
+            sys.stdout.buffer.write(ss.format_lines(hay, begin, end, number, line_numbers=True).cpu().numpy().tobytes())
         else:
-            begin, end, number = pat.find_lines(hay)
-            if device:
-                sys.stdout.buffer.write(ss.format_lines(hay, begin, end, number, line_numbers=True).cpu().numpy().tobytes())
-            else:
-                sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (n, data[b:e]) for b, e, n in zip(begin.cpu().tolist(), end.cpu().tolist(), number.cpu().tolist())))
+            sys.stdout.buffer.write(b"".join(b"%d:%s\n" % (n, data[b:e]) for b, e, n in zip(begin.cpu().tolist(), end.cpu().tolist(), number.cpu().tolist())))
+
+
+def classes_forms(argv, class_pattern, patterns, context, replacement, replace_map):
+    """--classes PATTERN [-i] (--count | --offsets | --count-lines | --lines) [--device-output] FILE: the byte-class calls."""
+    import torch
+    usage = "./grep_hip.py --classes '<pattern>' [-i] (--count | --offsets | --count-lines | --lines) [--device-output] <file>"
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    device = "--device-output" in flags
+    fold = "-i" in flags or "--ignore-case" in flags
+    modes = [f for f in flags if f not in ("--device-output", "-i", "--ignore-case")]
+    if class_pattern is None or len(args) != 1 or len(modes) != 1 or modes[0] not in ("--count", "--offsets", "--count-lines", "--lines") or \
+            patterns or context or replacement is not None or replace_map is not None or (device and modes[0] != "--lines"):
+        raise SystemExit(usage + ": --classes takes one pattern, one of the four modes and no other flag but -i (--device-output with --lines)")
+    with ss.classes_build():
+        try:
+            sets = ss.parse_classes(class_pattern, fold)            # (host only: a refused pattern never touches the device)
+        except (ss.SlicesliceError, UnicodeEncodeError) as e:
+            raise SystemExit("./grep_hip.py: --classes %r: %s" % (class_pattern, e))
+        data = open(args[0], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        try:
+            pat = ss.ClassPattern.from_sets(sets)
+        except ss.SlicesliceError as e:
+            raise SystemExit("./grep_hip.py: --classes %r: %s" % (class_pattern, e))
+        print_pattern_mode(pat, modes[0], device, hay, data)
 
 
 def main():
     argv, patterns, context, replacement, replace_map = [], [], {}, None, None
     hex_pattern, hex_given = None, False
+    class_pattern, classes_given = None, False
     it = iter(sys.argv[1:])
     for a in it:
         if a == "--replace":
@@ -265,6 +301,8 @@ def main():
             replace_map = next(it, None)
         elif a == "--hex":
             hex_given, hex_pattern = True, next(it, None)
+        elif a == "--classes":
+            classes_given, class_pattern = True, next(it, None)
         elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
@@ -283,8 +321,12 @@ def main():
             context["flag"] = flag
         else:
             argv.append(a)
+    if hex_given and classes_given:
+        raise SystemExit("./grep_hip.py: --hex and --classes are two pattern languages: give one")
     if hex_given:
         return hex_forms(argv, hex_pattern, patterns, context, replacement, replace_map)
+    if classes_given:
+        return classes_forms(argv, class_pattern, patterns, context, replacement, replace_map)
     fold = "-i" in argv or "--ignore-case" in argv
     word = "-w" in argv or "--word-regexp" in argv
     line = "-x" in argv or "--line-regexp" in argv
