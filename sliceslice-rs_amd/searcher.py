@@ -251,6 +251,24 @@ CLASSES_MAX_INEXACT = 1024          # SS_CLASSES_MAX_INEXACT: positions whose se
 CLASSES_MAX_DISTINCT = 64           # SS_CLASSES_MAX_DISTINCT: distinct sets among them
 # ss_classes_stats: eight 64-bit words, in this order
 CLASSES_STATS = ("n", "anchor", "distance", "single", "masked", "inexact", "distinct", "accepts_delimiter")
+# include/sliceslice_hip_runs.h: the maximal runs of one byte class (\\w+, [0-9]{3,}), counted and listed in ONE pass (runs and
+# matching lines) - libsliceslice_hip_runs.so only (the classes library's objects plus the run scan)
+RUNS_ABI = {
+    "ss_runs_new": (_int, [_vp, _u64, _u64, ctypes.c_uint, _pvp]),
+    "ss_runs_free": (None, [_vp]),
+    "ss_runs_info": (_int, [_vp, _int, _vp]),
+    "ss_runs_parse": (_int, [ctypes.c_char_p, _int, _vp, _pu64, _pu64]),
+    "ss_count_runs_device": (_int, [_vp, _vp, _sz, _vp, _pu64]),
+    "ss_count_runs_device_async": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ss_find_all_runs_device": (_int, [_vp, _vp, _sz, _vp, _vp, _vp, _u64, _pu64]),
+    "ss_count_lines_runs_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64]),
+    "ss_find_lines_runs_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
+RUNS_MAX_LEN = 4096                 # SS_RUNS_MAX_LEN: the largest min_len / max_len
+RUNS_MAX_RANGES = 4                 # SS_RUNS_MAX_RANGES: maximal ranges of a set on the range path
+SS_RUNS_BITMAP = 1                  # ss_runs_new flag: force the bitmap path
+# ss_runs_stats: six 64-bit words, in this order
+RUNS_STATS = ("min_len", "max_len", "members", "ranges", "path", "accepts_delimiter")
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -401,6 +419,10 @@ _FEATURES = {
                 "the byte-class calls (ss.ClassPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
                 "find_lines_into / info, ss.parse_classes, ss.classes_cover) are not part of this library: they live in "
                 "libsliceslice_hip_classes.so - create the pattern inside `with ss.classes_build():`"),
+    "runs": (RUNS_ABI, "ss_runs_new",
+             "the run calls (ss.RunPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
+             "find_lines_into / info, ss.parse_runs) are not part of this library: they live in "
+             "libsliceslice_hip_runs.so - create the pattern inside `with ss.runs_build():`"),
 }
 
 
@@ -592,6 +614,14 @@ class classes_build(_library_build):
     with ``count`` / ``count_async`` / ``find_all`` / ``find_all_into`` / ``count_lines`` / ``find_lines`` / ``find_lines_into`` /
     ``info`` of patterns created inside the block, and ``ss.parse_classes`` / ``ss.classes_cover``, which are host only)."""
     name = "classes"
+
+
+class runs_build(_library_build):
+    """libsliceslice_hip_runs.so: the classes library plus the MAXIMAL RUNS OF ONE BYTE CLASS, counted and listed in one pass
+    (include/sliceslice_hip_runs.h: ``ss.RunPattern(r"[0-9]{3,}")`` / ``.from_set`` with ``count`` / ``count_async`` / ``find_all`` /
+    ``find_all_into`` / ``count_lines`` / ``find_lines`` / ``find_lines_into`` / ``info`` of patterns created inside the block, and
+    ``ss.parse_runs``, which is host only)."""
+    name = "runs"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -1787,6 +1817,152 @@ class ClassPattern:
         L = getattr(self, "_L", None)
         if h and L is not None and _lib is not None:
             L.ss_classes_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_runs(text, ignore_case=False):
+    """(set, min_len, max_len): the four 64-bit words of the class and the bounds (``max_len`` None: no maximum) of a run pattern
+    such as ``r"\\w+"`` or ``r"[0-9]{3,}"`` (ss_runs_parse: ONE item of the classes language and one of ``+ {k} {k,} {k,m}``,
+    include/sliceslice_hip_runs.h).  Host only; inside ``with ss.runs_build():``."""
+    L = _feature_lib(lib(), "runs")
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    if b"\0" in raw:
+        raise SlicesliceError(SS_ERR_ARGUMENT, "ss_runs_parse: column %d: a NUL ends the text: write \\x00" % (raw.index(b"\0") + 1))
+    words = np.zeros(4, dtype=np.uint64)
+    lo, hi = _u64(0), _u64(0)
+    _check(L.ss_runs_parse(raw, int(bool(ignore_case)), words.ctypes.data, ctypes.byref(lo), ctypes.byref(hi)), L)
+    return words, int(lo.value), int(hi.value) or None
+
+
+class RunPattern:
+    """The maximal runs of one byte class whose length lies in ``[min_len, max_len]`` (ss_runs_new, inside ``with ss.runs_build():``)
+    on the current device: ``\\w+``, ``[0-9]{3,}``, ``[A-Z]{2,5}`` (include/sliceslice_hip_runs.h has the rule and the language of
+    ``text``).  A run that is too long is not selected and no run is chopped."""
+
+    def __init__(self, text, ignore_case=False):
+        self._h = None
+        self._L = _feature_lib(lib(), "runs")
+        words, lo, hi = parse_runs(text, ignore_case)
+        self._make(words, lo, hi, False)
+
+    def _make(self, words, min_len, max_len, bitmap):
+        L = self._L
+        h = ctypes.c_void_p()
+        _check(L.ss_runs_new(words.ctypes.data, int(min_len), int(max_len or 0), SS_RUNS_BITMAP if bitmap else 0, ctypes.byref(h)), L)
+        self._h = h
+        self.set, self.min_len, self.max_len = words, int(min_len), (int(max_len) if max_len else None)
+
+    @classmethod
+    def from_set(cls, set_words, min_len=1, max_len=None, bitmap=False):
+        """The pattern of four 64-bit words (byte b is bit ``b & 63`` of word ``b >> 6``); ``bitmap``: force the bitmap path."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._L = _feature_lib(lib(), "runs")
+        words = np.ascontiguousarray(np.asarray(set_words, dtype=np.uint64).reshape(-1))
+        if words.shape != (4,):
+            raise ValueError("a set is four 64-bit words, got shape %r" % (np.asarray(set_words).shape,))
+        self._make(words.copy(), min_len, max_len, bitmap)
+        return self
+
+    def info(self, delimiter=None):
+        """dict of ss_runs_info: min_len, max_len (0: none), members, ranges, path (0: range tests, 1: the bitmap),
+        accepts_delimiter (for ``delimiter``, if one is given)."""
+        words = (ctypes.c_uint64 * len(RUNS_STATS))()
+        _check(self._L.ss_runs_info(self._h, -1 if delimiter is None else _delimiter_byte(delimiter), words), self._L)
+        return dict(zip(RUNS_STATS, (int(w) for w in words)))
+
+    def count(self, haystack, stream=None):
+        """int: the selected runs (ss_count_runs_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_runs_device(self._h, ptr, length, st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def count_async(self, haystack, out=None, stream=None):
+        """ss_count_runs_device_async into ``out`` (a one-element int64 device tensor, made when None) and returns it:
+        stream-ordered, no wait, capturable into a graph."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if out is None:
+            out = torch.empty(1, dtype=torch.int64, device=t.device if t is not None else torch.device("cuda", torch.cuda.current_device()))
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_runs_device_async(self._h, ptr, length, st, out.data_ptr()), self._L)
+        return out
+
+    def find_all_into(self, haystack, d_begin, d_end, capacity=None, stream=None):
+        """ss_find_all_runs_device into the caller's 8-byte device tensors (either may be None; both with capacity 0); returns the
+        total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        if capacity is None:
+            capacity = min(x.numel() for x in (d_begin, d_end) if x is not None) if (d_begin is not None or d_end is not None) else 0
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end)]
+            _check(self._L.ss_find_all_runs_device(self._h, ptr, length, st, p[0], p[1], int(capacity), ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_all(self, haystack, capacity=None, stream=None):
+        """(begin, end) int64 device tensors: the first ``capacity`` (default: all, counted first) selected runs, ascending."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.find_all_into(hay, None, None, 0, stream)
+        out = torch.empty((2, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        total = self.find_all_into(hay, out[0] if capacity else None, out[1] if capacity else None, int(capacity), stream)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k]
+
+    def count_lines(self, haystack, delimiter=b"\n", stream=None):
+        """int: the lines that hold a selected run; the delimiter is never a member (ss_count_lines_runs_device)."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        c = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_lines_runs_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(c)), self._L)
+        return c.value
+
+    def find_lines_into(self, haystack, d_begin, d_end, d_number, capacity, delimiter=b"\n", stream=None):
+        """ss_find_lines_runs_device into the caller's 8-byte device tensors (each may be None); returns the total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+            _check(self._L.ss_find_lines_runs_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
+                                                     ctypes.byref(total)), self._L)
+        return total.value
+
+    def find_lines(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number) int64 device tensors of the first ``capacity`` (default: all, counted first) matching lines,
+        ascending - the records of ``DynamicHipSearcher.find_lines``."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            capacity = self.count_lines(hay, delimiter, stream)
+        out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        p = [out[k] if capacity else None for k in range(3)]
+        total = self.find_lines_into(hay, p[0], p[1], p[2], int(capacity), delimiter, stream)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k], out[2, :k]
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        L = getattr(self, "_L", None)
+        if h and L is not None and _lib is not None:
+            L.ss_runs_free(h)
 
     def __del__(self):
         try:

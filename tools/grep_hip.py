@@ -70,7 +70,13 @@ with --device-output the text of --lines is made on the device (ss_format_lines_
 pattern of byte classes in ONE pass (libsliceslice_hip_classes.so, include/sliceslice_hip_classes.h, which has the pattern language:
 a strict subset of Python `re` byte patterns under re.DOTALL), such as '[0-9A-F]{4}H', '\\d\\d:\\d\\d' or '[^a-z]the[^a-z]'.  The four modes
 and --device-output are those of --hex; -i is re.I.  Every other flag is refused, and a pattern the language refuses is reported
-with its column."""
+with its column.
+./grep_hip.py --runs '<pattern>' [-i] (--count | --offsets | -o | --count-lines | --lines) [--device-output] <file> - the maximal runs
+of ONE byte class in ONE pass (libsliceslice_hip_runs.so, include/sliceslice_hip_runs.h): one item of the classes language and one of
++ {k} {k,} {k,m}, such as '\\w+', '[0-9]{3,}' or '[A-Z]{2,5}'; a run that is too long is not selected and no run is chopped.  --count
+prints the number of selected runs, --offsets `begin:end` per run, -o the runs themselves, one per line (ss.gather_ranges: what
+`grep -o -E` prints when there is no maximum), --count-lines and --lines the lines that hold a selected run (--device-output as
+above); -i is re.I."""
 import os
 import sys
 
@@ -287,8 +293,39 @@ def classes_forms(argv, class_pattern, patterns, context, replacement, replace_m
         print_pattern_mode(pat, modes[0], device, hay, data)
 
 
+def runs_forms(argv, run_pattern, patterns, context, replacement, replace_map):
+    """--runs PATTERN [-i] (--count | --offsets | -o | --count-lines | --lines) [--device-output] FILE: the run calls."""
+    import torch
+    usage = "./grep_hip.py --runs '<pattern>' [-i] (--count | --offsets | -o | --count-lines | --lines) [--device-output] <file>"
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    device = "--device-output" in flags
+    fold = "-i" in flags or "--ignore-case" in flags
+    modes = [f for f in flags if f not in ("--device-output", "-i", "--ignore-case")]
+    if run_pattern is None or len(args) != 1 or len(modes) != 1 or modes[0] not in ("--count", "--offsets", "-o", "--count-lines", "--lines") or \
+            patterns or context or replacement is not None or replace_map is not None or (device and modes[0] != "--lines"):
+        raise SystemExit(usage + ": --runs takes one pattern, one of the five modes and no other flag but -i (--device-output with --lines)")
+    with ss.runs_build():
+        try:
+            words, lo, hi = ss.parse_runs(run_pattern, fold)        # (host only: a refused pattern never touches the device)
+        except (ss.SlicesliceError, UnicodeEncodeError) as e:
+            raise SystemExit("./grep_hip.py: --runs %r: %s" % (run_pattern, e))
+        data = open(args[0], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        pat = ss.RunPattern.from_set(words, lo, hi)
+        if modes[0] == "--offsets":
+            begin, end = pat.find_all(hay)
+            sys.stdout.buffer.write(b"".join(b"%d:%d\n" % (b, e) for b, e in zip(begin.cpu().tolist(), end.cpu().tolist())))
+        elif modes[0] == "-o":
+            begin, end = pat.find_all(hay)
+            if begin.numel():
+                sys.stdout.buffer.write(ss.gather_ranges(hay, begin, end, b"\n").cpu().numpy().tobytes())
+        else:
+            print_pattern_mode(pat, modes[0], device, hay, data)
+
+
 def main():
     argv, patterns, context, replacement, replace_map = [], [], {}, None, None
+    run_pattern, runs_given = None, False
     hex_pattern, hex_given = None, False
     class_pattern, classes_given = None, False
     it = iter(sys.argv[1:])
@@ -303,6 +340,8 @@ def main():
             hex_given, hex_pattern = True, next(it, None)
         elif a == "--classes":
             classes_given, class_pattern = True, next(it, None)
+        elif a == "--runs":
+            runs_given, run_pattern = True, next(it, None)
         elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
@@ -321,8 +360,10 @@ def main():
             context["flag"] = flag
         else:
             argv.append(a)
-    if hex_given and classes_given:
-        raise SystemExit("./grep_hip.py: --hex and --classes are two pattern languages: give one")
+    if hex_given + classes_given + runs_given > 1:
+        raise SystemExit("./grep_hip.py: --hex, --classes and --runs are three pattern languages: give one")
+    if runs_given:
+        return runs_forms(argv, run_pattern, patterns, context, replacement, replace_map)
     if hex_given:
         return hex_forms(argv, hex_pattern, patterns, context, replacement, replace_map)
     if classes_given:
