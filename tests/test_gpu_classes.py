@@ -2,7 +2,8 @@
 numpy (tests/test_classes_cpu.py: rule_offsets, rule_lines), against the searchers and the masked patterns of the same build, and
 against tests/golden/classes_kat.json (Python's re).  Every comparison is of integers and exact; every output array is a window of
 a larger one whose sentinels on both sides must survive.  The geometry's units are lane 16 B, piece 1 KiB, wave 4 KiB, tile 16 KiB
-and workgroup 128 KiB, so - the manual's text aside - no view is larger than 300,000 bytes (two workgroups and a tail)."""
+and workgroup 128 KiB, so - the manual's text aside - no view is larger than 300,000 bytes (two workgroups and a tail); views of
+more than one chunk of 256 workgroups are tests/test_gpu_set_grids.py's."""
 import hashlib
 import json
 import os

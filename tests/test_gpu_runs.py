@@ -2,7 +2,8 @@
 (tests/test_runs_cpu.py: rule_runs, rule_lines), against calls of the same build that exist, and against tests/golden/runs_kat.json
 (Python's re).  Every comparison is of integers and exact; every output array is a window of a larger one whose sentinels on both
 sides must survive.  The geometry's units are lane 16 B, piece 1 KiB, wave 4 KiB, tile 16 KiB and workgroup 128 KiB, so - the
-manual's text aside - no view is larger than 300 KiB (two workgroups and a tail)."""
+manual's text aside - no view is larger than 300 KiB (two workgroups and a tail); views of more than one chunk of 256 workgroups are
+tests/test_gpu_set_grids.py's."""
 import json
 import os
 
@@ -187,6 +188,82 @@ def test_capacities_with_either_array_left_out_and_a_run_across_the_workgroup_bo
         assert (b.cpu().numpy() == begin).all() and (e.cpu().numpy() == end).all()
         b, e = pat.find_all(dev, capacity=5)
         assert b.cpu().tolist() == begin[:5].tolist() and e.cpu().tolist() == end[:5].tolist()
+
+
+def test_the_line_calls_under_capacities_with_each_array_left_out(ss):
+    """find_lines_into on the two-workgroup haystack above: no room, one record, the lines closed in the first workgroup and one
+    fewer and one more, all but one, all; each of begin, end and number left out in turn.  The total is returned every time."""
+    rng = np.random.default_rng(33)
+    host = haystack(WORD, 0.6, 2 * WG + 5000, rng)
+    host[WG - 40:WG + 3 + 40] = ord("w")
+    arena = Arena(host)
+    dev, view = arena.view(3, host.size - 3)
+    for lo, hi, bitmap in ((1, None, False), (3, None, True), (2, 6, False)):
+        pat = make(ss, WORD, lo, hi, bitmap)
+        want = rule_lines(view, WORD, lo, hi, 10)
+        total = want[0].size
+        first = int((want[1] < WG - 3).sum())                       # the delimiter lies in the first workgroup
+        assert 2 < first < total - 2 and int((want[1] >= 2 * WG - 3).sum()) > 0
+        for cap in sorted({0, 1, first - 1, first, first + 1, total - 1, total}):
+            for skip in (None, 0, 1, 2) if cap else (None,):
+                ws = [Window(max(cap, 1)) for _ in range(3)]
+                args = [None if (k == skip or cap == 0) else ws[k].view for k in range(3)]
+                assert pat.find_lines_into(dev, args[0], args[1], args[2], cap) == total, (lo, hi, cap, skip)
+                for k, name in enumerate(("begin", "end", "number")):
+                    ws[k].check(want[k][:cap] if args[k] is not None else [], (lo, hi, bitmap, cap, skip, name))
+
+
+# ---- runs that the 32-bit window leaves undecided -------------------------------------------------------------------------------
+WALKS = (((33, 40), (32, 33, 40, 41)), ((4096, None), (4095, 4096)), ((1, 4096), (4096, 4097)), ((4096, 4096), (4095, 4096, 4097)))
+
+
+@pytest.mark.parametrize("bounds,lengths", WALKS, ids=["%d-%s" % b for b, _ in WALKS])
+def test_runs_that_only_a_walk_decides_across_every_border_and_cut_by_the_view(ss, bounds, lengths):
+    """Runs of [a-z] as long as the bounds, one byte shorter and one byte longer, laid across a piece, a wave, a tile and a workgroup
+    border with 1, 16, 17 and L - 1 bytes in front, on both paths at misalignment 0 and 5.  Then every run cut by a view: one that
+    begins k bytes into it (the member bytes that memory holds in front of the view are absent) and one that ends k bytes before
+    its end, with k such that lo - 1, lo, hi and hi + 1 bytes stay visible."""
+    letters = sets_of(re_set(r"[a-z]"))[0]
+    lo, hi = bounds
+    pats = [make(ss, letters, lo, hi, bitmap) for bitmap in (False, True)]
+    assert [p.info()["path"] for p in pats] == [0, 1]
+    borders = (5 * PIECE, 3 * WAVE, 2 * TILE, WG)                   # each a border of its unit and of no larger one
+    assert all(x % u == 0 and x % (4 * u) != 0 for x, u in zip(borders, (PIECE, WAVE, TILE, WG)))
+    size = WG + 4200 + 16
+    cuts = 0
+    for length in lengths:
+        selected = lo <= length <= (hi or length)
+        for front in (1, 16, 17, length - 1):
+            host = np.full(size, ord("-"), dtype=np.uint8)
+            for x in borders:
+                host[x - front:x - front + length] = ord("q")
+            b, e = rule_runs(host, letters)
+            assert b.tolist() == [x - front for x in borders] and (e - b == length).all()
+            arena = Arena(host)
+            for mis in (0, 5):                                      # the arena's offsets are the geometry's: the borders stay
+                dev, view = arena.view(mis, size - 16)
+                want = rule_runs(view, letters, lo, hi)
+                assert want[0].size == (4 if selected else 0)
+                for pat in pats:
+                    check_runs(pat, dev, want[0], want[1], (bounds, length, front, mis, pat.info()["path"]))
+            for rb in b.tolist():
+                for visible in sorted({lo - 1, lo} | ({hi, hi + 1} if hi else set())):
+                    k = length - visible
+                    if not 0 < k < length:
+                        continue
+                    views = [arena.view(rb + k, length - k + 64)]                       # begins k bytes into the run
+                    for mis in (0, 5):                                                  # ends k bytes before the run's end
+                        begin = (rb - 64) // 16 * 16 + mis
+                        views.append(arena.view(begin, rb + length - k - begin))
+                    for j, (dev, view) in enumerate(views):
+                        want = rule_runs(view, letters, lo, hi)
+                        assert want[0].size == (1 if lo <= visible <= (hi or visible) else 0)
+                        if want[0].size:
+                            assert (want[0][0], want[1][0]) == ((0, visible) if j == 0 else (view.size - visible, view.size))
+                        for pat in pats:
+                            check_runs(pat, dev, want[0], want[1], (bounds, length, front, rb, visible, j, pat.info()["path"]))
+                        cuts += 1
+    assert cuts >= 3 * 4 * 4                                        # (some run was cut on both sides at every border and front)
 
 
 def test_the_two_paths_agree_on_sets_of_one_to_four_ranges_and_info_reports_the_path(ss):

@@ -2,7 +2,8 @@
 ss_needle_set_ranks, ss_count_set_device / _async and ss_find_all_set_device against the rule restated on Python bytes, against
 arithmetic where the text is uniform, against `count` / `find_all` of one searcher per needle of the SAME build merged by
 (offset, rank), and against tests/golden/bounded_kat.json.  Every comparison is of integers and exact; every output array is a
-window of a larger one whose sentinels on both sides must survive.  The manual's text aside, no view is larger than three workgroups."""
+window of a larger one whose sentinels on both sides must survive.  The manual's text aside, no view is larger than three workgroups;
+views of more than one chunk of 256 workgroups are tests/test_gpu_set_grids.py's."""
 import json
 import os
 import subprocess
