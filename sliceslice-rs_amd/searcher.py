@@ -269,6 +269,12 @@ RUNS_MAX_RANGES = 4                 # SS_RUNS_MAX_RANGES: maximal ranges of a se
 SS_RUNS_BITMAP = 1                  # ss_runs_new flag: force the bitmap path
 # ss_runs_stats: six 64-bit words, in this order
 RUNS_STATS = ("min_len", "max_len", "members", "ranges", "path", "accepts_delimiter")
+# include/sliceslice_hip_rewrite.h: the selected runs of one byte class replaced or deleted on the device (tr -d, sed s/[0-9]+/N/g) -
+# libsliceslice_hip_rewrite.so only (the runs library's objects plus the rewrite)
+REWRITE_ABI = {
+    "ss_replace_runs_device": (_int, [_vp, _vp, _sz, _int, _vp, _sz, _vp, _vp, _u64, _pu64, _pu64]),
+}
+SS_REWRITE_MAX_TEXT = 4096          # the longest replacement
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -423,6 +429,9 @@ _FEATURES = {
              "the run calls (ss.RunPattern: count / count_async / find_all / find_all_into / count_lines / find_lines / "
              "find_lines_into / info, ss.parse_runs) are not part of this library: they live in "
              "libsliceslice_hip_runs.so - create the pattern inside `with ss.runs_build():`"),
+    "rewrite": (REWRITE_ABI, "ss_replace_runs_device",
+                "the rewrite calls (ss.RunPattern: replace / replace_into / delete) are not part of this library: they live in "
+                "libsliceslice_hip_rewrite.so - create the pattern inside `with ss.rewrite_build():`"),
 }
 
 
@@ -622,6 +631,13 @@ class runs_build(_library_build):
     ``find_all_into`` / ``count_lines`` / ``find_lines`` / ``find_lines_into`` / ``info`` of patterns created inside the block, and
     ``ss.parse_runs``, which is host only)."""
     name = "runs"
+
+
+class rewrite_build(_library_build):
+    """libsliceslice_hip_rewrite.so: the runs library plus the SELECTED RUNS REPLACED OR DELETED on the device
+    (include/sliceslice_hip_rewrite.h: ``replace`` / ``replace_into`` / ``delete`` of ``ss.RunPattern`` objects created inside the
+    block - ``tr -d``, ``tr -s``, ``sed -E 's/[0-9]+/N/g'``; they take a ``delimiter`` that is never a member)."""
+    name = "rewrite"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -1957,6 +1973,46 @@ class RunPattern:
         total = self.find_lines_into(hay, p[0], p[1], p[2], int(capacity), delimiter, stream)
         k = min(int(capacity), total)
         return out[0, :k], out[1, :k], out[2, :k]
+
+    # -- the selected runs replaced or deleted (libsliceslice_hip_rewrite.so: patterns made inside `with ss.rewrite_build():`) ------
+    def replace_into(self, haystack, text, d_out, delimiter=None, stream=None):
+        """ss_replace_runs_device into the caller's uint8 device tensor ``d_out`` (None: the sizing call, one pass); returns
+        ``(out_len, count)``.  Nothing is written where ``d_out`` holds fewer than ``out_len`` bytes.  ``text`` is host bytes, at
+        most SS_REWRITE_MAX_TEXT of them, and may be empty; ``delimiter`` (None: none) is a byte that is never a member here."""
+        L = _feature_lib(self._L, "rewrite")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        keep, addr, rn = _host_view(bytes(text))
+        out_len, c = _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(L.ss_replace_runs_device(self._h, ptr, length, -1 if delimiter is None else _delimiter_byte(delimiter), addr, rn, st,
+                                            d_out.data_ptr() if d_out is not None else None, d_out.numel() if d_out is not None else 0,
+                                            ctypes.byref(out_len), ctypes.byref(c)), L)
+        return out_len.value, c.value
+
+    def replace(self, haystack, text, delimiter=None, stream=None):
+        """uint8 tensor on the haystack's device: the haystack with every selected run replaced by ``text`` - ``re.sub`` of the
+        pattern.  A text of at most ``min_len`` bytes cannot make the output longer than the view: one call into a buffer of the
+        view's size; any other text is sized first."""
+        import torch
+        _feature_lib(self._L, "rewrite")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        text = bytes(text)
+        if len(text) <= self.min_len:
+            out = torch.empty(max(length, 1), dtype=torch.uint8, device=dev)
+            out_len, _ = self.replace_into(hay, text, out[:length], delimiter, stream)
+            return out[:out_len]
+        out_len, _ = self.replace_into(hay, text, None, delimiter, stream)
+        out = torch.empty(max(out_len, 1), dtype=torch.uint8, device=dev)
+        if out_len:
+            out_len, _ = self.replace_into(hay, text, out[:out_len], delimiter, stream)
+        return out[:min(out_len, out.numel() if out_len else 0)]
+
+    def delete(self, haystack, delimiter=None, stream=None):
+        """``replace`` with the empty text: the haystack without its selected runs (``tr -d``)."""
+        return self.replace(haystack, b"", delimiter, stream)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

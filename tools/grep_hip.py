@@ -76,7 +76,11 @@ of ONE byte class in ONE pass (libsliceslice_hip_runs.so, include/sliceslice_hip
 + {k} {k,} {k,m}, such as '\\w+', '[0-9]{3,}' or '[A-Z]{2,5}'; a run that is too long is not selected and no run is chopped.  --count
 prints the number of selected runs, --offsets `begin:end` per run, -o the runs themselves, one per line (ss.gather_ranges: what
 `grep -o -E` prints when there is no maximum), --count-lines and --lines the lines that hold a selected run (--device-output as
-above); -i is re.I."""
+above); -i is re.I.
+./grep_hip.py --runs '<pattern>' [-i] --replace <text> [--per-line] <file> - the file with every selected run replaced by <text>, on
+stdout (libsliceslice_hip_rewrite.so, include/sliceslice_hip_rewrite.h: `sed -E 's/<pattern>/<text>/g'`, `tr -d`, `tr -s`); an empty
+<text> deletes; --per-line passes the delimiter `\n`, which is then never a member, so that '\\s+' works line by line as in sed.  It
+is not combined with the five listing modes."""
 import os
 import sys
 
@@ -293,9 +297,38 @@ def classes_forms(argv, class_pattern, patterns, context, replacement, replace_m
         print_pattern_mode(pat, modes[0], device, hay, data)
 
 
+def runs_replace_form(argv, run_pattern, patterns, context, replacement, replace_map):
+    """--runs PATTERN [-i] --replace TEXT [--per-line] FILE: the substituted file on stdout (ss.RunPattern.replace)."""
+    import torch
+    usage = "./grep_hip.py --runs '<pattern>' [-i] --replace <text> [--per-line] <file>"
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    fold = "-i" in flags or "--ignore-case" in flags
+    listing = [f for f in flags if f in ("--count", "--offsets", "-o", "--count-lines", "--lines")]
+    if listing:
+        raise SystemExit(usage + ": --replace writes the substituted file and is not combined with %s" % " ".join(listing))
+    other = [f for f in flags if f not in ("-i", "--ignore-case", "--replace", "--per-line")]
+    if run_pattern is None or replacement is None or len(args) != 1 or other or patterns or context or replace_map is not None:
+        raise SystemExit(usage + ": --runs with --replace takes one pattern, one text, one file and no other flag but -i and --per-line")
+    with ss.rewrite_build():
+        try:
+            words, lo, hi = ss.parse_runs(run_pattern, fold)        # (host only: a refused pattern never touches the device)
+            text = replacement.encode("latin-1")
+        except (ss.SlicesliceError, UnicodeEncodeError) as e:
+            raise SystemExit("./grep_hip.py: --runs %r: %s" % (run_pattern, e))
+        data = open(args[0], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        try:
+            out = ss.RunPattern.from_set(words, lo, hi).replace(hay, text, b"\n" if "--per-line" in flags else None)
+        except ss.SlicesliceError as e:
+            raise SystemExit("./grep_hip.py: --runs %r --replace: %s" % (run_pattern, e))
+        sys.stdout.buffer.write(out.cpu().numpy().tobytes())
+
+
 def runs_forms(argv, run_pattern, patterns, context, replacement, replace_map):
     """--runs PATTERN [-i] (--count | --offsets | -o | --count-lines | --lines) [--device-output] FILE: the run calls."""
     import torch
+    if replacement is not None or "--replace" in argv or "--per-line" in argv:
+        return runs_replace_form(argv, run_pattern, patterns, context, replacement, replace_map)
     usage = "./grep_hip.py --runs '<pattern>' [-i] (--count | --offsets | -o | --count-lines | --lines) [--device-output] <file>"
     args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
     device = "--device-output" in flags
