@@ -275,6 +275,21 @@ REWRITE_ABI = {
     "ss_replace_runs_device": (_int, [_vp, _vp, _sz, _int, _vp, _sz, _vp, _vp, _u64, _pu64, _pu64]),
 }
 SS_REWRITE_MAX_TEXT = 4096          # the longest replacement
+# include/sliceslice_hip_fields.h: fields first .. last of every line located on the device (cut -f, awk '{print $k}') -
+# libsliceslice_hip_fields.so only (the rewrite library's objects plus the field scan)
+FIELDS_ABI = {
+    "ss_fields_new": (_int, [_vp, _int, _u64, _u64, ctypes.c_uint, _pvp]),
+    "ss_fields_free": (None, [_vp]),
+    "ss_fields_info": (_int, [_vp, _int, _vp]),
+    "ss_fields_parse": (_int, [ctypes.c_char_p, _pu64, _pu64]),
+    "ss_count_fields_device": (_int, [_vp, _vp, _sz, _int, _vp, _pu64, _pu64]),
+    "ss_find_fields_device": (_int, [_vp, _vp, _sz, _int, _vp, _vp, _vp, _vp, _u64, _pu64]),
+}
+SS_FIELDS_EACH, SS_FIELDS_MERGE = 0, 1      # ss_fields_new modes: every separator ends a field (cut) / runs of separators do (awk)
+SS_FIELDS_KEEP_SHORT = 1            # ss_fields_new flag: an empty record for every line that is not selected
+FIELDS_CARRY_CHUNK = 256            # SS_FIELDS_CARRY_CHUNK: workgroup summaries per step of the carry kernel
+# ss_fields_stats: six 64-bit words, in this order
+FIELDS_STATS = ("mode", "first", "last", "flags", "members", "accepts_delimiter")
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -432,6 +447,9 @@ _FEATURES = {
     "rewrite": (REWRITE_ABI, "ss_replace_runs_device",
                 "the rewrite calls (ss.RunPattern: replace / replace_into / delete) are not part of this library: they live in "
                 "libsliceslice_hip_rewrite.so - create the pattern inside `with ss.rewrite_build():`"),
+    "fields": (FIELDS_ABI, "ss_fields_new",
+               "the field calls (ss.FieldSelector: count / find / find_into / cut / info, ss.parse_fields) are not part of this "
+               "library: they live in libsliceslice_hip_fields.so - create the selector inside `with ss.fields_build():`"),
 }
 
 
@@ -638,6 +656,14 @@ class rewrite_build(_library_build):
     (include/sliceslice_hip_rewrite.h: ``replace`` / ``replace_into`` / ``delete`` of ``ss.RunPattern`` objects created inside the
     block - ``tr -d``, ``tr -s``, ``sed -E 's/[0-9]+/N/g'``; they take a ``delimiter`` that is never a member)."""
     name = "rewrite"
+
+
+class fields_build(_library_build):
+    """libsliceslice_hip_fields.so: the rewrite library plus FIELDS first .. last OF EVERY LINE, located on the device
+    (include/sliceslice_hip_fields.h: ``ss.FieldSelector(b",", 3)`` / ``ss.FieldSelector(r"[ \\t]", 2, merge=True)`` with ``count`` /
+    ``find`` / ``find_into`` / ``cut`` / ``info`` of selectors created inside the block - ``cut -d, -f3``, ``awk '{print $2}'`` - and
+    ``ss.parse_fields``, which is host only)."""
+    name = "fields"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -2019,6 +2045,118 @@ class RunPattern:
         L = getattr(self, "_L", None)
         if h and L is not None and _lib is not None:
             L.ss_runs_free(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_fields(text):
+    """(first, last): cut's single range ``K``, ``K-``, ``K-M`` or ``-M`` (ss_fields_parse, include/sliceslice_hip_fields.h);
+    ``last`` 0 means "to the line's end".  A comma list is refused: make one call per range.  Host only; inside
+    ``with ss.fields_build():``."""
+    L = _feature_lib(lib(), "fields")
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    if b"\0" in raw:
+        raise SlicesliceError(SS_ERR_ARGUMENT, "ss_fields_parse: column %d: a NUL ends the text" % (raw.index(b"\0") + 1))
+    lo, hi = _u64(0), _u64(0)
+    _check(L.ss_fields_parse(raw, ctypes.byref(lo), ctypes.byref(hi)), L)
+    return int(lo.value), int(hi.value)
+
+
+class FieldSelector:
+    """Fields ``first .. last`` of every line (ss_fields_new, inside ``with ss.fields_build():``) on the current device:
+    ``cut -d, -f3`` is ``FieldSelector(b",", 3)``, ``awk '{print $2}'`` is ``FieldSelector(r"[ \\t]", 2, merge=True)``
+    (include/sliceslice_hip_fields.h has the rule).  ``separator``: a bytes object of members, ONE item of the classes language as a
+    str (``r"[ \\t]"``, ``","``), or four 64-bit words.  ``last=None`` means ``last = first``, ``last=0`` "to the line's end".
+    ``keep_short``: an empty record for every line that is not selected, so that record k is line k + 1."""
+
+    def __init__(self, separator, first, last=None, merge=False, keep_short=False):
+        self._h = None
+        L = self._L = _feature_lib(lib(), "fields")
+        if isinstance(separator, (bytes, bytearray)):
+            words = np.zeros(4, dtype=np.uint64)
+            for b in bytes(separator):
+                words[b >> 6] |= np.uint64(1 << (b & 63))
+        elif isinstance(separator, str):
+            sets = parse_classes(separator)
+            if len(sets) != 1:
+                raise ValueError("the separator is ONE item of the classes language, %r has %d" % (separator, len(sets)))
+            words = sets[0].copy()
+        else:
+            words = np.ascontiguousarray(np.asarray(separator, dtype=np.uint64).reshape(-1)).copy()
+            if words.shape != (4,):
+                raise ValueError("a set is four 64-bit words, got shape %r" % (np.asarray(separator).shape,))
+        first = int(first)
+        last = first if last is None else int(last)
+        mode = SS_FIELDS_MERGE if merge else SS_FIELDS_EACH
+        flags = SS_FIELDS_KEEP_SHORT if keep_short else 0
+        h = ctypes.c_void_p()
+        _check(L.ss_fields_new(words.ctypes.data, mode, first, last, flags, ctypes.byref(h)), L)
+        self._h = h
+        self.set, self.first, self.last, self.merge, self.keep_short = words, first, last, bool(merge), bool(keep_short)
+
+    def info(self, delimiter=None):
+        """dict of ss_fields_info: mode, first, last (0: to the line's end), flags, members, accepts_delimiter (for ``delimiter``,
+        if one is given)."""
+        words = (ctypes.c_uint64 * len(FIELDS_STATS))()
+        _check(self._L.ss_fields_info(self._h, -1 if delimiter is None else _delimiter_byte(delimiter), words), self._L)
+        return dict(zip(FIELDS_STATS, (int(w) for w in words)))
+
+    def count(self, haystack, delimiter=b"\n", stream=None):
+        """(selected, total): the lines that have field ``first``, and all lines (ss_count_fields_device); one pass."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        sel, tot = _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            _check(self._L.ss_count_fields_device(self._h, ptr, length, _delimiter_byte(delimiter), st, ctypes.byref(sel), ctypes.byref(tot)), self._L)
+        return sel.value, tot.value
+
+    def find_into(self, haystack, d_begin, d_end, d_number, capacity=None, delimiter=b"\n", stream=None):
+        """ss_find_fields_device into the caller's 8-byte device tensors (each may be None; all three with capacity 0); returns the
+        total."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        given = [x for x in (d_begin, d_end, d_number) if x is not None]
+        if capacity is None:
+            capacity = min(x.numel() for x in given) if given else 0
+        total = _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None else None for x in (d_begin, d_end, d_number)]
+            _check(self._L.ss_find_fields_device(self._h, ptr, length, _delimiter_byte(delimiter), st, p[0], p[1], p[2], int(capacity),
+                                                 ctypes.byref(total)), self._L)
+        return total.value
+
+    def find(self, haystack, delimiter=b"\n", capacity=None, stream=None):
+        """(begin, end, number) int64 device tensors: the first ``capacity`` (default: all, counted first) records, ascending."""
+        import torch
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        if capacity is None:
+            sel, tot = self.count(hay, delimiter, stream)
+            capacity = tot if self.keep_short else sel
+        out = torch.empty((3, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+        p = [out[k] if capacity else None for k in range(3)]
+        total = self.find_into(hay, p[0], p[1], p[2], int(capacity), delimiter, stream)
+        k = min(int(capacity), total)
+        return out[0, :k], out[1, :k], out[2, :k]
+
+    def cut(self, haystack, terminator=b"\n", delimiter=b"\n", stream=None):
+        """uint8 device tensor: the selected fields of every record, each followed by ``terminator`` (None: none) - ``find``
+        followed by ``ss.gather_ranges``: what ``cut -f`` prints."""
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        hay = t if t is not None else (ptr, length)
+        begin, end, _ = self.find(hay, delimiter, None, stream)
+        return _format(self._L, hay, begin, end, None, None, terminator, 0, stream, gather=True)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        L = getattr(self, "_L", None)
+        if h and L is not None and _lib is not None:
+            L.ss_fields_free(h)
 
     def __del__(self):
         try:

@@ -80,7 +80,15 @@ above); -i is re.I.
 ./grep_hip.py --runs '<pattern>' [-i] --replace <text> [--per-line] <file> - the file with every selected run replaced by <text>, on
 stdout (libsliceslice_hip_rewrite.so, include/sliceslice_hip_rewrite.h: `sed -E 's/<pattern>/<text>/g'`, `tr -d`, `tr -s`); an empty
 <text> deletes; --per-line passes the delimiter `\n`, which is then never a member, so that '\\s+' works line by line as in sed.  It
-is not combined with the five listing modes."""
+is not combined with the five listing modes.
+./grep_hip.py --fields <list> -d <sep> [--merge] [-s] [--device-output] <file> - fields first .. last of every line, one line of output
+per record (libsliceslice_hip_fields.so, include/sliceslice_hip_fields.h: `cut -d, -f3`, `awk '{print $2}'`).  <list> is cut's single
+range K, K-, K-M or -M (a comma list is refused: one call per range); <sep> is one character or one item of the classes language
+such as '[ \\t]'; --merge takes runs of separators as one and ignores leading and trailing ones, as awk does.  -s prints nothing for a
+line that lacks field `first`; without it such a line gives an empty line, so that the output has one line per input line.  With
+--device-output the text is gathered on the device (ss.gather_ranges) and comes to the host in one copy.  THE ONE DIFFERENCE FROM
+cut: a line without any separator is treated as a line with one field - cut prints such a line whole, whatever the list says.
+./grep_hip.py --help prints this text."""
 import os
 import sys
 
@@ -356,9 +364,37 @@ def runs_forms(argv, run_pattern, patterns, context, replacement, replace_map):
             print_pattern_mode(pat, modes[0], device, hay, data)
 
 
+def fields_form(argv, field_list, separator):
+    """--fields LIST -d SEP [--merge] [-s] [--device-output] FILE: the selected fields, one line per record (ss.FieldSelector)."""
+    import torch
+    usage = "./grep_hip.py --fields <list> -d <sep> [--merge] [-s] [--device-output] <file>"
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    other = [f for f in flags if f not in ("--merge", "-s", "--device-output")]
+    if field_list is None or not separator or len(args) != 1 or other:
+        raise SystemExit(usage + ": --fields takes one range, one separator, one file and no other flag but --merge, -s and --device-output")
+    with ss.fields_build():
+        try:
+            first, last = ss.parse_fields(field_list)               # (host only: a refused list never touches the device)
+            sep = separator.encode("latin-1") if len(separator) == 1 else separator
+            sel = ss.FieldSelector(sep, first, last, merge="--merge" in flags, keep_short="-s" not in flags)
+        except (ss.SlicesliceError, UnicodeEncodeError, ValueError) as e:
+            raise SystemExit("./grep_hip.py: --fields %r -d %r: %s" % (field_list, separator, e))
+        data = open(args[0], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        if "--device-output" in flags:
+            sys.stdout.buffer.write(sel.cut(hay).cpu().numpy().tobytes())
+        else:
+            begin, end, _ = sel.find(hay)
+            sys.stdout.buffer.write(b"".join(data[b:e] + b"\n" for b, e in zip(begin.cpu().tolist(), end.cpu().tolist())))
+
+
 def main():
+    if "--help" in sys.argv[1:]:
+        print(__doc__)
+        return None
     argv, patterns, context, replacement, replace_map = [], [], {}, None, None
     run_pattern, runs_given = None, False
+    field_list, fields_given, separator = None, False, None
     hex_pattern, hex_given = None, False
     class_pattern, classes_given = None, False
     it = iter(sys.argv[1:])
@@ -375,6 +411,10 @@ def main():
             classes_given, class_pattern = True, next(it, None)
         elif a == "--runs":
             runs_given, run_pattern = True, next(it, None)
+        elif a == "--fields":
+            fields_given, field_list = True, next(it, None)
+        elif a == "-d" and "--fields" in sys.argv:
+            separator = next(it, None)
         elif a == "-e":
             patterns.append(next(it).encode())
         elif a == "-f":
@@ -395,6 +435,10 @@ def main():
             argv.append(a)
     if hex_given + classes_given + runs_given > 1:
         raise SystemExit("./grep_hip.py: --hex, --classes and --runs are three pattern languages: give one")
+    if fields_given:
+        if hex_given or classes_given or runs_given or patterns or context or replacement is not None or replace_map is not None:
+            raise SystemExit("./grep_hip.py: --fields selects columns and is not combined with a pattern, context, -e / -f or --replace")
+        return fields_form(argv, field_list, separator)
     if runs_given:
         return runs_forms(argv, run_pattern, patterns, context, replacement, replace_map)
     if hex_given:
