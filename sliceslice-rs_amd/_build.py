@@ -3,7 +3,7 @@
     libsliceslice_hip.so          the product: include/sliceslice_hip.h and nothing else (-fvisibility=hidden)
     libsliceslice_hip_<name>.so   the opt-in libraries of LIBRARIES below (service, matches, matches_batched, lines, nocase, bounded,
                                   inverted, context, anyof, needleset, setmatches, disjoint) and of the mappings under it (output,
-                                  leftmost, masked, classes, runs, rewrite, fields): the
+                                  leftmost, masked, classes, runs, rewrite, fields, groups): the
                                   objects of the library's parent (the product's, where it has none) plus its own sources, which
                                   define include/sliceslice_hip_<name>.h - a process uses ONE library: the product or one of these
     libsliceslice_hip_tools.so    benchmark helpers (synthetic haystack generator, read ceiling, self-test): ss_tools.hip
@@ -81,6 +81,9 @@ _REWRITE_LIBRARIES = {"rewrite": _library("rewrite", "runs", ["ss_rewrite.hip"])
 # ... and the nineteenth, in a sixth mapping for the same reason: fields first .. last of every line located on the device
 # (include/sliceslice_hip_fields.h).
 _FIELDS_LIBRARIES = {"fields": _library("fields", "rewrite", ["ss_fields.hip"])}
+# ... and the twentieth, in a seventh mapping for the same reason: equal tokens or lines grouped and counted on the device
+# (include/sliceslice_hip_groups.h).
+_GROUPS_LIBRARIES = {"groups": _library("groups", "fields", ["ss_groups.hip"])}
 _SERVICE_SOURCES = LIBRARIES["service"]["sources"]
 # The tuning build adds every variant ss_searcher_set_variant can name: plain loads, U = 8.
 _TUNING_SOURCES = _SOURCES + _SERVICE_SOURCES + ["scan_inst_u4_nt0.hip", "scan_inst_find_nt0.hip", "scan_inst_u8_nt0.hip", "scan_inst_u8_nt1.hip"]
@@ -253,7 +256,7 @@ def build(force=False, verbose=False):
 
 def _lib(name):
     """The entry of library `name` (KeyError: there is none)."""
-    for table in (LIBRARIES, _FIELDS_LIBRARIES, _REWRITE_LIBRARIES, _NEWEST_LIBRARIES, _LATEST_LIBRARIES):
+    for table in (LIBRARIES, _GROUPS_LIBRARIES, _FIELDS_LIBRARIES, _REWRITE_LIBRARIES, _NEWEST_LIBRARIES, _LATEST_LIBRARIES):
         if name in table:
             return table[name]
     return _LATER_LIBRARIES[name]
@@ -301,7 +304,7 @@ def _wrappers(name):
 
 
 for _name in (list(LIBRARIES) + list(_LATER_LIBRARIES) + list(_LATEST_LIBRARIES) + list(_NEWEST_LIBRARIES) + list(_REWRITE_LIBRARIES) +
-              list(_FIELDS_LIBRARIES)):
+              list(_FIELDS_LIBRARIES) + list(_GROUPS_LIBRARIES)):
     globals().update(_wrappers(_name))
 
 

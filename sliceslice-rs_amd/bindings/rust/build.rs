@@ -1,6 +1,6 @@
 // The drop-in library (libsliceslice_hip.so: include/sliceslice_hip.h) - and, with the `hip-service` feature, the library that
 // holds the resident search service as well (libsliceslice_hip_service.so: the same objects plus ss_service.hip), linked INSTEAD.
-// The other opt-in libraries (hip_matches.rs ... hip_setmatches.rs, hip_disjoint.rs, hip_output.rs, hip_leftmost.rs, hip_masked.rs, hip_classes.rs, hip_runs.rs, hip_rewrite.rs, hip_fields.rs) are built by sliceslice-rs_amd/_build.py; a crate
+// The other opt-in libraries (hip_matches.rs ... hip_setmatches.rs, hip_disjoint.rs, hip_output.rs, hip_leftmost.rs, hip_masked.rs, hip_classes.rs, hip_runs.rs, hip_rewrite.rs, hip_fields.rs, hip_groups.rs) are built by sliceslice-rs_amd/_build.py; a crate
 // that enables one of their features links that library instead.
 fn main() {
     let out = std::env::var("OUT_DIR").unwrap();

@@ -290,6 +290,20 @@ SS_FIELDS_KEEP_SHORT = 1            # ss_fields_new flag: an empty record for ev
 FIELDS_CARRY_CHUNK = 256            # SS_FIELDS_CARRY_CHUNK: workgroup summaries per step of the carry kernel
 # ss_fields_stats: six 64-bit words, in this order
 FIELDS_STATS = ("mode", "first", "last", "flags", "members", "accepts_delimiter")
+# include/sliceslice_hip_groups.h: equal tokens or lines grouped and counted on the device (sort | uniq -c, awk '!seen[$0]++') -
+# libsliceslice_hip_groups.so only (the fields library's objects plus the grouping)
+GROUPS_ABI = {
+    "ss_group_ranges_device": (_int, [_vp, _sz, _vp, _vp, _u64, ctypes.c_uint, _vp, _vp, _vp, _u64, _vp, _pu64]),
+    "ss_group_runs_device": (_int, [_vp, _vp, _sz, ctypes.c_uint, _vp, _vp, _vp, _vp, _u64, _pu64, _pu64]),
+    "ss_group_lines_device": (_int, [_vp, _sz, _int, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _u64, _pu64, _pu64]),
+    "ss_groups_scratch_bytes": (_int, [_u64, _pu64]),
+}
+SS_GROUPS_NOCASE = 1                # flag of the grouping calls: every key byte goes through the ASCII fold
+SS_GROUPS_WEAK_HASH = 2             # ... for tests: the hash is length & 3, four probe chains
+GROUPS_MAX_RANGES = 2 ** 32 - 2     # SS_GROUPS_MAX_RANGES: ranges of a call
+GROUPS_BLOCK = 4096                 # SS_GROUPS_BLOCK: ranges per rank block
+GROUPS_LANE_MAX = 128               # SS_GROUPS_LANE_MAX: the longest key one lane hashes and compares alone
+GROUPS_LDS_BYTES = 24576            # SS_GROUPS_LDS_BYTES: the count kernel's workgroup-private table
 # include/sliceslice_hip_tuning.h, group 1: libsliceslice_hip_tools.so
 TOOLS_ABI = {
     "ss_fill_random_device": (_int, [_vp, _u64, _sz, _u64, _vp]),
@@ -450,6 +464,10 @@ _FEATURES = {
     "fields": (FIELDS_ABI, "ss_fields_new",
                "the field calls (ss.FieldSelector: count / find / find_into / cut / info, ss.parse_fields) are not part of this "
                "library: they live in libsliceslice_hip_fields.so - create the selector inside `with ss.fields_build():`"),
+    "groups": (GROUPS_ABI, "ss_group_ranges_device",
+               "the grouping calls (ss.group_ranges / group_ranges_into / group_lines / groups_scratch_bytes, ss.RunPattern: groups / "
+               "most_common) are not part of this library: they live in libsliceslice_hip_groups.so - call them, and create the "
+               "pattern, inside `with ss.groups_build():`"),
 }
 
 
@@ -664,6 +682,14 @@ class fields_build(_library_build):
     ``find`` / ``find_into`` / ``cut`` / ``info`` of selectors created inside the block - ``cut -d, -f3``, ``awk '{print $2}'`` - and
     ``ss.parse_fields``, which is host only)."""
     name = "fields"
+
+
+class groups_build(_library_build):
+    """libsliceslice_hip_groups.so: the fields library plus EQUAL TOKENS OR LINES GROUPED AND COUNTED on the device
+    (include/sliceslice_hip_groups.h: ``ss.group_ranges`` / ``ss.group_ranges_into`` over any list of ranges, ``groups`` /
+    ``most_common`` of ``ss.RunPattern`` objects created inside the block - ``grep -oE '\\w+' | sort | uniq -c`` - ``ss.group_lines`` -
+    ``sort | uniq -c``, ``awk '!seen[$0]++'`` - and ``ss.groups_scratch_bytes``, which is host only)."""
+    name = "groups"
 
 
 _FOLD_TABLE = bytes(b | 0x20 if 0x41 <= b <= 0x5A else b for b in range(256))
@@ -2040,6 +2066,52 @@ class RunPattern:
         """``replace`` with the empty text: the haystack without its selected runs (``tr -d``)."""
         return self.replace(haystack, b"", delimiter, stream)
 
+    # -- the selected runs grouped and counted (libsliceslice_hip_groups.so: patterns made inside `with ss.groups_build():`) --------
+    def groups_into(self, haystack, d_begin, d_end, d_count, capacity=None, ignore_case=False, stream=None, weak_hash=False):
+        """ss_group_runs_device into the caller's 8-byte device tensors (each may be None; capacity: default the shortest of them,
+        0 where all are None); returns ``(groups, tokens)``."""
+        L = _feature_lib(self._L, "groups")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        given = [x for x in (d_begin, d_end, d_count) if x is not None]
+        if capacity is None:
+            capacity = min(x.numel() for x in given) if given else 0
+        groups, tokens = _u64(0), _u64(0)
+        with _on_device_of(t):
+            st = stream if stream is not None else _current_stream_handle()
+            p = [x.data_ptr() if x is not None and x.numel() else None for x in (d_begin, d_end, d_count)]
+            _check(L.ss_group_runs_device(self._h, ptr, length, _groups_flags(ignore_case, weak_hash), st, p[0], p[1], p[2], int(capacity),
+                                          ctypes.byref(groups), ctypes.byref(tokens)), L)
+        return groups.value, tokens.value
+
+    def groups(self, haystack, ignore_case=False, stream=None, weak_hash=False):
+        """(begin, end, count) int64 device tensors, one row per DISTINCT selected run in first-occurrence order: the first run
+        with those bytes and how many there are - ``collections.Counter(re.findall(...))`` without leaving the device
+        (ss_group_runs_device with room for _GROUPS_ROWS rows: one call for a vocabulary of that size; a larger one REPEATS THE
+        WHOLE CALL, sized - call ``groups_into`` with room for every row where that matters).  ``ss.gather_ranges(haystack, begin, end, b"\\n")`` prints the vocabulary.  ``ignore_case`` folds ASCII letters
+        before keys are compared."""
+        import torch
+        _feature_lib(self._L, "groups")
+        ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+        dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+        hay = t if t is not None else (ptr, length)
+        out = torch.empty((3, _GROUPS_ROWS), dtype=torch.int64, device=dev)
+        total, _ = self.groups_into(hay, out[0], out[1], out[2], _GROUPS_ROWS, ignore_case, stream, weak_hash)
+        if total > _GROUPS_ROWS:
+            out = torch.empty((3, total), dtype=torch.int64, device=dev)
+            again, _ = self.groups_into(hay, out[0], out[1], out[2], total, ignore_case, stream, weak_hash)
+            total = min(total, again)
+        return out[0, :total], out[1, :total], out[2, :total]
+
+    def most_common(self, haystack, k=None, ignore_case=False, stream=None):
+        """(begin, end, count) of the ``k`` (None: all) most frequent distinct runs, most frequent first, ties in first-occurrence
+        order - ``Counter.most_common(k)``: ``groups`` and a stable descending sort of the counts on the device."""
+        import torch
+        begin, end, count = self.groups(haystack, ignore_case, stream)
+        order = torch.sort(count, descending=True, stable=True).indices
+        if k is not None:
+            order = order[:max(int(k), 0)]
+        return begin[order], end[order], count[order]
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         L = getattr(self, "_L", None)
@@ -2163,6 +2235,109 @@ class FieldSelector:
             self.close()
         except Exception:
             pass
+
+
+# The grouping calls (include/sliceslice_hip_groups.h): functions of the module, since no handle owns them.
+_GROUPS_ROWS = 1 << 16      # rows RunPattern.groups and group_lines make room for before they know the number of groups
+
+
+def _groups_flags(ignore_case, weak_hash=False):
+    return (SS_GROUPS_NOCASE if ignore_case else 0) | (SS_GROUPS_WEAK_HASH if weak_hash else 0)
+
+
+def groups_scratch_bytes(n):
+    """int: the temporary device memory a grouping call over ``n`` ranges takes (ss_groups_scratch_bytes; the run and the line
+    form take 16 bytes per range more).  Host only; inside ``with ss.groups_build():``."""
+    L = _feature_lib(lib(), "groups")
+    n = int(n)
+    if not 0 <= n <= _U64_MAX:
+        raise ValueError("n is a number of ranges, 0 .. 2^64 - 1, got %d" % n)
+    out = _u64(0)
+    _check(L.ss_groups_scratch_bytes(n, ctypes.byref(out)), L)
+    return int(out.value)
+
+
+def group_ranges_into(haystack, begin, end, d_first, d_count, d_group=None, capacity=None, ignore_case=False, stream=None, weak_hash=False):
+    """ss_group_ranges_device into the caller's 8-byte device tensors (each may be None; capacity: default the shorter of
+    ``d_first`` and ``d_count``, 0 where both are None; ``d_group`` holds one entry per range); returns the number of groups.
+    Inside ``with ss.groups_build():``."""
+    import torch
+    L = _feature_lib(lib(), "groups")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    dev = t.device if t is not None else (begin.device if _is_tensor(begin) and begin.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    given = [x for x in (d_first, d_count) if x is not None]
+    if capacity is None:
+        capacity = min(x.numel() for x in given) if given else 0
+    groups = _u64(0)
+    with _on_device_of(t if t is not None else begin):
+        b, e = _device_numbers(begin, dev).reshape(-1), _device_numbers(end, dev).reshape(-1)
+        if b.numel() != e.numel():
+            raise ValueError("%d begins and %d ends" % (b.numel(), e.numel()))
+        if d_group is not None and d_group.numel() < b.numel():
+            raise ValueError("d_group holds one entry per range: %d, got %d" % (b.numel(), d_group.numel()))
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None and x.numel() else None for x in (b, e, d_first, d_count, d_group)]
+        _check(L.ss_group_ranges_device(ptr, length, p[0], p[1], b.numel(), _groups_flags(ignore_case, weak_hash), st, p[2], p[3], int(capacity),
+                                        p[4], ctypes.byref(groups)), L)
+    return groups.value
+
+
+def group_ranges(haystack, begin, end, ignore_case=False, capacity=None, want_group=False, stream=None, weak_hash=False):
+    """The ranges [begin[k], end[k]) of ``haystack`` - sequences, arrays or device tensors; they may overlap, repeat and descend
+    and are clamped to the haystack - grouped by their bytes: ``(first, count)`` int64 device tensors with one row per distinct key
+    in first-occurrence order (``first[j]`` is the smallest k of group j, ``count[j]`` its members: a ``collections.Counter`` filled
+    in input order), the first ``capacity`` rows (default: all); ``want_group``: and ``group``, the j of every range
+    (ss_group_ranges_device).  ``ignore_case`` folds ASCII letters before keys are compared.  Inside ``with ss.groups_build():``."""
+    import torch
+    _feature_lib(lib(), "groups")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    dev = t.device if t is not None else (begin.device if _is_tensor(begin) and begin.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    hay = t if t is not None else (ptr, length)
+    b, e = _device_numbers(begin, dev).reshape(-1), _device_numbers(end, dev).reshape(-1)
+    group = torch.empty(max(b.numel(), 1), dtype=torch.int64, device=dev)[:b.numel()] if want_group else None
+    if capacity is None:
+        # all rows: there are at most n of them, and one call fills them
+        capacity = b.numel()
+    out = torch.empty((2, max(int(capacity), 1)), dtype=torch.int64, device=dev)
+    total = group_ranges_into(hay, b, e, out[0] if capacity else None, out[1] if capacity else None, group, int(capacity), ignore_case, stream,
+                              weak_hash)
+    k = min(int(capacity), total)
+    return (out[0, :k], out[1, :k], group) if want_group else (out[0, :k], out[1, :k])
+
+
+def group_lines_into(haystack, d_begin, d_end, d_number, d_count, capacity=None, delimiter=b"\n", ignore_case=False, stream=None, weak_hash=False):
+    """ss_group_lines_device into the caller's 8-byte device tensors (each may be None); returns ``(groups, lines)``."""
+    L = _feature_lib(lib(), "groups")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    given = [x for x in (d_begin, d_end, d_number, d_count) if x is not None]
+    if capacity is None:
+        capacity = min(x.numel() for x in given) if given else 0
+    groups, lines = _u64(0), _u64(0)
+    with _on_device_of(t):
+        st = stream if stream is not None else _current_stream_handle()
+        p = [x.data_ptr() if x is not None and x.numel() else None for x in (d_begin, d_end, d_number, d_count)]
+        _check(L.ss_group_lines_device(ptr, length, _delimiter_byte(delimiter), _groups_flags(ignore_case, weak_hash), st, p[0], p[1], p[2], p[3],
+                                       int(capacity), ctypes.byref(groups), ctypes.byref(lines)), L)
+    return groups.value, lines.value
+
+
+def group_lines(haystack, delimiter=b"\n", ignore_case=False, stream=None, weak_hash=False):
+    """(begin, end, number, count) int64 device tensors, one row per DISTINCT line of ``haystack`` in first-occurrence order: the
+    record and the number of the first line with those bytes (the delimiter is no part of them; empty lines are lines) and how many
+    there are - ``sort | uniq -c`` before the sort, ``awk '!seen[$0]++'`` (ss_group_lines_device with room for _GROUPS_ROWS rows;
+    where there are more the WHOLE call is repeated, sized - ``group_lines_into`` with room for every row does it once).  Inside ``with ss.groups_build():``."""
+    import torch
+    _feature_lib(lib(), "groups")
+    ptr, length, t = DynamicHipSearcher._device_haystack(haystack)
+    dev = t.device if t is not None else torch.device("cuda", torch.cuda.current_device())
+    hay = t if t is not None else (ptr, length)
+    out = torch.empty((4, _GROUPS_ROWS), dtype=torch.int64, device=dev)
+    total, _ = group_lines_into(hay, out[0], out[1], out[2], out[3], _GROUPS_ROWS, delimiter, ignore_case, stream, weak_hash)
+    if total > _GROUPS_ROWS:
+        out = torch.empty((4, total), dtype=torch.int64, device=dev)
+        again, _ = group_lines_into(hay, out[0], out[1], out[2], out[3], total, delimiter, ignore_case, stream, weak_hash)
+        total = min(total, again)
+    return out[0, :total], out[1, :total], out[2, :total], out[3, :total]
 
 
 class DynamicHipSearcher:

@@ -88,6 +88,13 @@ such as '[ \\t]'; --merge takes runs of separators as one and ignores leading an
 line that lacks field `first`; without it such a line gives an empty line, so that the output has one line per input line.  With
 --device-output the text is gathered on the device (ss.gather_ranges) and comes to the host in one copy.  THE ONE DIFFERENCE FROM
 cut: a line without any separator is treated as a line with one field - cut prints such a line whole, whatever the list says.
+./grep_hip.py --runs '<pattern>' --uniq-count [-i] [--top <k>] [--device-output] <file> - `count<TAB>token` per DISTINCT selected run, in
+first-occurrence order (libsliceslice_hip_groups.so, include/sliceslice_hip_groups.h: `grep -oE '<pattern>' | sort | uniq -c` before
+the sort, a collections.Counter filled in input order).  --top <k> prints the k most frequent, most frequent first, ties in
+first-occurrence order.  -i folds ASCII letters before tokens are compared; the token printed is the first occurrence as it stands.
+With --device-output the tokens are gathered on the device (ss.gather_ranges) and come to the host in one copy.
+./grep_hip.py --lines-uniq-count [-i] [--top <k>] [--device-output] <file> - the same for whole lines: sorted, this is `sort | uniq -c`.
+./grep_hip.py --uniq [-i] [--device-output] <file> - every distinct line once, in input order (`awk '!seen[$0]++'`).
 ./grep_hip.py --help prints this text."""
 import os
 import sys
@@ -388,11 +395,66 @@ def fields_form(argv, field_list, separator):
             sys.stdout.buffer.write(b"".join(data[b:e] + b"\n" for b, e in zip(begin.cpu().tolist(), end.cpu().tolist())))
 
 
+def print_groups(hay, data, begin, end, count, device, counted=True):
+    """`count<TAB>key` per row (counted=False: the key alone).  device: the keys are gathered on the device (ss.gather_ranges) and come
+    to the host in one copy with their starts; otherwise the rows come and the host slices the file."""
+    if begin.numel() == 0:
+        return
+    counts = count.cpu().tolist()
+    if device:
+        text, starts = ss.gather_ranges(hay, begin, end, b"\n", return_starts=True)
+        if not counted:
+            sys.stdout.buffer.write(text.cpu().numpy().tobytes())
+            return
+        text, starts = text.cpu().numpy().tobytes(), starts.cpu().tolist()
+        keys = (text[starts[k]:starts[k + 1]] for k in range(len(counts)))
+    else:
+        keys = (data[b:e] + b"\n" for b, e in zip(begin.cpu().tolist(), end.cpu().tolist()))
+    sys.stdout.buffer.write(b"".join(key if not counted else b"%d\t%s" % (c, key) for c, key in zip(counts, keys)))
+
+
+def top_amount(text):
+    if text is None or not (text.isascii() and text.isdigit()):
+        raise SystemExit("./grep_hip.py: --top takes a non-negative integer (a number of rows), got %r" % (text,))
+    return int(text)
+
+
+def groups_forms(argv, run_pattern, top):
+    """--runs PATTERN --uniq-count [-i] [--top K] [--device-output] FILE, --lines-uniq-count [-i] [--top K] [--device-output] FILE and
+    --uniq [-i] [--device-output] FILE: the grouping calls (ss.RunPattern.groups / most_common, ss.group_lines)."""
+    import torch
+    usage = ("./grep_hip.py --runs '<pattern>' --uniq-count [-i] [--top <k>] [--device-output] <file>\n"
+             "./grep_hip.py (--lines-uniq-count [--top <k>] | --uniq) [-i] [--device-output] <file>")
+    args, flags = [a for a in argv if not a.startswith("-")], [a for a in argv if a.startswith("-")]
+    device = "--device-output" in flags
+    fold = "-i" in flags or "--ignore-case" in flags
+    modes = [f for f in flags if f not in ("--device-output", "-i", "--ignore-case")]
+    if len(args) != 1 or len(modes) != 1 or (modes[0] == "--uniq-count") != (run_pattern is not None) or (modes[0] == "--uniq" and top is not None):
+        raise SystemExit(usage + ": one mode, one file; --uniq-count goes with --runs, the two line modes without; --top not with --uniq")
+    with ss.groups_build():
+        data = open(args[0], "rb").read()
+        hay = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda() if data else torch.empty(0, dtype=torch.uint8, device="cuda")
+        if run_pattern is not None:
+            try:
+                words, lo, hi = ss.parse_runs(run_pattern, fold)    # (host only: a refused pattern never touches the device)
+            except (ss.SlicesliceError, UnicodeEncodeError) as e:
+                raise SystemExit("./grep_hip.py: --runs %r: %s" % (run_pattern, e))
+            pat = ss.RunPattern.from_set(words, lo, hi)
+            begin, end, count = pat.groups(hay, ignore_case=fold) if top is None else pat.most_common(hay, top, ignore_case=fold)
+        else:
+            begin, end, _, count = ss.group_lines(hay, ignore_case=fold)
+            if top is not None:
+                order = torch.sort(count, descending=True, stable=True).indices[:top]
+                begin, end, count = begin[order], end[order], count[order]
+        print_groups(hay, data, begin, end, count, device, counted=modes[0] != "--uniq")
+
+
 def main():
     if "--help" in sys.argv[1:]:
         print(__doc__)
         return None
     argv, patterns, context, replacement, replace_map = [], [], {}, None, None
+    top = None
     run_pattern, runs_given = None, False
     field_list, fields_given, separator = None, False, None
     hex_pattern, hex_given = None, False
@@ -411,6 +473,8 @@ def main():
             classes_given, class_pattern = True, next(it, None)
         elif a == "--runs":
             runs_given, run_pattern = True, next(it, None)
+        elif a == "--top":
+            top = top_amount(next(it, None))
         elif a == "--fields":
             fields_given, field_list = True, next(it, None)
         elif a == "-d" and "--fields" in sys.argv:
@@ -435,6 +499,15 @@ def main():
             argv.append(a)
     if hex_given + classes_given + runs_given > 1:
         raise SystemExit("./grep_hip.py: --hex, --classes and --runs are three pattern languages: give one")
+    if "--uniq-count" in argv or "--lines-uniq-count" in argv or "--uniq" in argv:
+        if hex_given or classes_given or fields_given or patterns or context or replacement is not None or replace_map is not None:
+            raise SystemExit("./grep_hip.py: --uniq-count, --lines-uniq-count and --uniq group tokens or lines and are not combined with "
+                             "--hex, --classes, --fields, context, -e / -f or --replace")
+        if runs_given and run_pattern is None:
+            raise SystemExit("./grep_hip.py: --runs takes a pattern")
+        return groups_forms(argv, run_pattern if runs_given else None, top)
+    if top is not None:
+        raise SystemExit("./grep_hip.py: --top goes with --uniq-count or --lines-uniq-count")
     if fields_given:
         if hex_given or classes_given or runs_given or patterns or context or replacement is not None or replace_map is not None:
             raise SystemExit("./grep_hip.py: --fields selects columns and is not combined with a pattern, context, -e / -f or --replace")
